@@ -23,10 +23,19 @@ A step = one full pass of the hot path over device-resident inputs:
   --workload q1 / q3: BASELINE configs 4 and 5 — the whole TPC-H Q1 / Q3 plan per step (queries.q1 / q3: Partial
           aggregate -> hash exchange of the states -> FinalPartitioned; Q3's four repartitions in two phases), rows of
           the scanned tables per second.
-value = (input rows summed over ranks) / max-over-ranks wall time of the K steps.
-Inputs are generated on device (no dataset download possible) before the timed region.
+value = (input rows summed over ranks) / max-over-ranks wall time of the K steps; ms_per_step = that wall time / K.
+Inputs are generated on device (no dataset download possible) before the timed region, the same rows for the same arguments.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the K steps and prints the line (with the `roofline` and `kernels` objects the timed steps'
+own HIP events give).  Everything that takes runs of its own — the ordered_output step, the cpu_baseline leg, BASELINE configs 4
+and 5 under `also`, the planner's pruned exchange at N > 1, Q3's intermediate row counts and the oracle's check of the Q1 / Q3
+result — runs only with --full.
+
+  --dump-outputs DIR  after the timed steps, what the last timed step computed goes to DIR/<name>.npy (float64): the join's output
+                      columns as a seeded sample of its rows (chosen by a hash of l_orderkey, sorted by every column, at most 48 MB)
+                      plus <workload>_totals.npy (row count and per-column sums of the whole output); Q1 / Q3 their whole result.
+
+Extra objects on the JSON line (roofline on every line, ordered_output and cpu_baseline with --full):
   roofline     — dominant kernel (join_probe_fused = k_join_probe_fused: lookup + output offsets +
                  materialisation in one pass; join_probe_placed = the same kernel placed by pre-computed tile
                  offsets when --probe-mode 0): algorithmic bytes per launch (probe columns read once
@@ -260,13 +269,151 @@ def setup_dist(args):
 
 
 def timed(step, steps, barrier):
+    """the last step holds on to its output (hold=True) for --dump-outputs; the caller frees it after the timed region"""
     barrier()
     t0 = time.perf_counter()
     last = None
-    for _ in range(steps):
-        last = step()
+    for i in range(steps):
+        last = step(hold=i == steps - 1)
     barrier()
     return time.perf_counter() - t0, last
+
+
+DUMP_BYTES = 48 << 20         # what --dump-outputs may write in all (the limit is 64 MB)
+DUMP_SEED = 20260601          # picks the sampled rows' hash residue: a fixed sample for fixed arguments
+_HASH_A, _HASH_P = 48271, 2147483647
+
+
+def host_arrays(tab):
+    """an Arrow table's columns as float64 numpy arrays (name -> array): decimals by value, dates as days since the epoch, strings as
+    one row of UTF-8 bytes per value (zero padded), nulls as NaN"""
+    import numpy as np
+    import pyarrow as pa
+    out = {}
+    for name, c in zip(tab.column_names, tab.columns):
+        c = c.combine_chunks() if isinstance(c, pa.ChunkedArray) else c
+        if pa.types.is_dictionary(c.type):
+            c = c.dictionary_decode()
+        t = c.type
+        if pa.types.is_string(t) or pa.types.is_large_string(t) or pa.types.is_binary(t) or pa.types.is_large_binary(t) or t == pa.string_view():
+            vals = [v.encode() if isinstance(v, str) else v for v in c.to_pylist()]
+            a = np.zeros((len(vals), max([len(v) for v in vals if v is not None], default=0) or 1))
+            for i, v in enumerate(vals):
+                if v is None:
+                    a[i] = np.nan
+                else:
+                    a[i, :len(v)] = np.frombuffer(v, dtype=np.uint8)
+        else:
+            if pa.types.is_date32(t):
+                c = c.cast(pa.int32())
+            elif pa.types.is_date64(t) or pa.types.is_timestamp(t):
+                c = c.cast(pa.int64())
+            a = c.cast(pa.float64()).to_numpy(zero_copy_only=False).astype(np.float64)
+        out[name] = a
+    return out
+
+
+def sample_rows(key, m, r, chunk=1 << 26):
+    """indices (int64 tensor on key's device) of the rows whose key hashes to residue r of m: (key * 48271 mod (2^31 - 1)) mod m == r,
+    a fixed sample of a large output whatever order its rows come in; taken `chunk` rows at a time"""
+    import torch
+    parts = []
+    for b in range(0, key.numel(), chunk):
+        k = key[b:b + chunk].to(torch.int64)
+        parts.append(torch.nonzero(((k * _HASH_A) % _HASH_P) % m == r).flatten() + b)
+    return torch.cat(parts) if parts else torch.zeros(0, dtype=torch.int64, device=key.device)
+
+
+def canonical_order(cols):
+    """the permutation that sorts rows by every column, the first the most significant (a stable sort per column, last column first)"""
+    import torch
+    n = cols[0].numel() if cols else 0
+    order = torch.arange(n, device=cols[0].device if cols else "cpu")
+    for c in reversed(cols):
+        order = order[torch.sort(c[order], stable=True).indices]
+    return order
+
+
+def _device_columns(table):
+    """zero-copy torch views of a device table's fixed-width columns: (name, type, scale, values, validity bytes or None)"""
+    import torch
+
+    from datafusion_amd import table as T
+    from datafusion_amd.exchange import _as_tensor
+    cols = []
+    for i in range(table.num_columns):
+        v = table.column_view(i)
+        name, n, ty = v.name.decode(), v.length, v.field.type
+        width = {T.INT32: 4, T.DATE32: 4, T.UINT32: 4, T.INT64: 8, T.UINT64: 8, T.FLOAT64: 8, T.UINT8: 1, T.DECIMAL128: 16}.get(ty)
+        if width is None:
+            raise TypeError(f"--dump-outputs: column {name} (dfgpu type {ty}) has no device dump")
+        raw = _as_tensor(v.data, n * width)
+        vals = raw.view({1: torch.uint8, 4: torch.int32, 8: torch.float64 if ty == T.FLOAT64 else torch.int64, 16: torch.int64}[width])
+        if ty == T.DECIMAL128:
+            vals = vals.view(n, 2)
+        valid = _as_tensor(v.validity, (n + 7) // 8) if (v.validity and v.null_count > 0) else None
+        cols.append((name, ty, v.field.scale, vals, valid))
+    return cols
+
+
+def _as_f64(ty, vals, idx=None):
+    """one column's values (at rows idx, or all of them) as float64; decimals unscaled (the scale is applied on the host: a GPU
+    tensor divided by a Python number is multiplied by its reciprocal, which is not always the correctly rounded quotient)"""
+    import torch
+
+    from datafusion_amd import table as T
+    x = vals if idx is None else vals[idx]
+    if ty == T.DECIMAL128:
+        lo, hi = x[:, 0], x[:, 1]
+        return (hi - (lo >> 63)).to(torch.float64) * 2.0 ** 64 + lo.to(torch.float64)
+    if ty == T.UINT32:
+        return (x.to(torch.int64) & 0xFFFFFFFF).to(torch.float64)
+    return x.to(torch.float64)
+
+
+def dump_device_table(table, out_dir, prefix, key, expected_rows):
+    """a large device-resident output: the rows whose `key` hashes into a fixed residue (about DUMP_BYTES of them, the residue's
+    modulus from `expected_rows`, an input size, so that the sample does not move with the output) in canonical order, one
+    DIR/<prefix>_<column>.npy each, and DIR/<prefix>_totals.npy = [rows, sum of each column] over the whole output"""
+    import numpy as np
+    import torch
+
+    from datafusion_amd import table as T
+    cols = _device_columns(table)
+    cap = max(1, DUMP_BYTES // (8 * len(cols) + 8))
+    m = max(1, -(-int(expected_rows) // cap))
+    k = next(i for i, c in enumerate(cols) if c[0] == key)
+    key_vals = cols[k][3]
+    idx = sample_rows(key_vals if key_vals.dim() == 1 else key_vals[:, 0], m, DUMP_SEED % m)
+    vals = []
+    for name, ty, scale, v, valid in cols:
+        f = _as_f64(ty, v, idx)
+        if valid is not None:
+            f = torch.where(((valid[idx >> 3].to(torch.int64) >> (idx & 7)) & 1) == 1, f, torch.full_like(f, float("nan")))
+        vals.append(f)
+    order = canonical_order([vals[k]] + vals[:k] + vals[k + 1:])[:cap]
+    for (name, ty, scale, *_), f in zip(cols, vals):
+        a = f[order].cpu().numpy()
+        np.save(os.path.join(out_dir, f"{prefix}_{name}.npy"), a / 10.0 ** scale if ty == T.DECIMAL128 else a)
+    totals = [float(table.num_rows)]
+    for name, ty, scale, v, _valid in cols:
+        if v.dim() == 2:   # decimal: the sum of the signed low words plus the carried high words, scaled
+            lo, hi = v[:, 0], v[:, 1]
+            totals.append((float((hi - (lo >> 63)).sum()) * 2.0 ** 64 + float(lo.sum())) / 10.0 ** scale)
+        elif v.dtype == torch.float64:
+            totals.append(float(v.sum()))
+        else:   # integers summed exactly (an unsigned 32-bit column is read as int32: each negative value is 2^32 short)
+            wrap = float((v < 0).sum()) * 2.0 ** 32 if v.dtype == torch.int32 and ty == T.UINT32 else 0.0
+            totals.append(float(v.sum(dtype=torch.int64)) + wrap)
+    np.save(os.path.join(out_dir, f"{prefix}_totals.npy"), np.array(totals, dtype=np.float64))
+    torch.cuda.empty_cache()    # the temporaries' HBM goes back before the library allocates again
+
+
+def dump_arrow(tab, out_dir, prefix):
+    """a small result whole, in the order the caller receives it: DIR/<prefix>_<column>.npy"""
+    import numpy as np
+    for name, a in host_arrays(tab).items():
+        np.save(os.path.join(out_dir, f"{prefix}_{name}.npy"), a)
 
 
 def max_over_ranks(dist, dt, *sums):
@@ -315,7 +462,8 @@ def run_join(args, rank, world, dist):
             dist.barrier()
 
     def make_step(exchange, probe_mode):
-        def step():
+        def step(hold=False):
+            """(output rows, join info, the output table when `hold`, else None: the caller frees it)"""
             o, l = orders, lineitem
             if exchange == "pruned":
                 o = comm.broadcast_pruned(orders, "o_orderkey", lineitem, "l_orderkey")
@@ -339,7 +487,7 @@ def run_join(args, rank, world, dist):
                     n_out += out.num_rows
                     out.free()
                     chunk.free()
-                res = (n_out, ht.info())
+                res = (n_out, ht.info(), None)
                 ht.free()
                 return res
             # join-table choice follows the library default (direct-address down to key density 1/64, see
@@ -347,8 +495,9 @@ def run_join(args, rank, world, dist):
             # same key range (density 0.25/N)
             ht = ops.JoinHashTable(o, ["o_orderkey"], probe_mode=probe_mode)
             out = ht.probe(l, ["l_orderkey"], "Inner", BUILD_COLS, PROBE_COLS)
-            res = (out.num_rows, ht.info())
-            out.free()
+            res = (out.num_rows, ht.info(), out if hold else None)
+            if not hold:
+                out.free()
             ht.free()
             if o is not orders:
                 o.free()
@@ -357,7 +506,8 @@ def run_join(args, rank, world, dist):
             return res
         return step
 
-    def measure(exchange, probe_mode, profile):
+    def measure(exchange, probe_mode, profile, keep=False):
+        """warm-up + timed steps; keep=True: the last step's output stays in the result ("held") for --dump-outputs"""
         step = make_step(exchange, probe_mode)
         for _ in range(args.warmup):
             step()
@@ -366,13 +516,16 @@ def run_join(args, rank, world, dist):
         if profile:
             ops.profile_enable(True)
             ops.profile_reset()
-        dt, (n_out, info) = timed(step, args.steps, barrier)
+        dt, (n_out, info, held) = timed(step, args.steps, barrier)
         st = ops.profile_stats() if profile else {}
         if profile:
             ops.profile_enable(False)
         xs = comm.stats(reset=True) if comm is not None else None
         dt, (nb, np_, nout) = max_over_ranks(dist, dt, nb_local, np_local, n_out)
-        return {"dt": dt, "nb": nb, "np": np_, "nout": nout, "info": info, "stats": st, "xstats": xs}
+        if held is not None and not keep:
+            held.free()
+            held = None
+        return {"dt": dt, "nb": nb, "np": np_, "nout": nout, "info": info, "stats": st, "xstats": xs, "held": held}
 
     if world == 1 and not forced:
         primary = "none"
@@ -479,7 +632,7 @@ def run_join(args, rank, world, dist):
                                       "rows_per_s": (nb + np_) / (oms * 1e-3),
                                       "hbm_frac_whole_step": round(alg / (oms * 1e-3) / 1e9 / (HBM_PEAK_GBS * world), 4),
                                       "roofline": roofline_of(ordered["stats"]), "kernels": kernel_table(ordered["stats"])}
-        if final and not args.no_cpu and world == 1:  # the CPU baseline is reported by the single-GPU run only
+        if final and args.full and not args.no_cpu and world == 1:  # the CPU baseline is reported by the single-GPU run only
             threads = os.cpu_count() or 1
             line["cpu_baseline"] = cpu_baseline(args.sf, args.sf if args.cpu_sf is None else args.cpu_sf, threads, orders, lineitem)
             # a ratio only between equal workloads: the same tables, the same payload, the same scale factor
@@ -497,7 +650,7 @@ def run_join(args, rank, world, dist):
         checkpoint(None, None, "repartition")
         m = measure("repartition", args.probe_mode, True)
         primary = "repartition"
-        for ex in (("repartition_stream",) if args.exchange_chunks > 1 else ()) + ("pruned",):
+        for ex in (("repartition_stream",) if args.exchange_chunks > 1 else ()) + (("pruned",) if args.full else ()):
             checkpoint(m, primary, ex)
             if exchange_errors:
                 # an exchange that failed part-way may have left the ranks out of step inside the communicator: nothing more runs on it
@@ -511,13 +664,17 @@ def run_join(args, rank, world, dist):
             others["repartition"], m, primary = m, others.pop("repartition_stream"), "repartition_stream"
     else:
         checkpoint(None, None, primary)
-        m = measure(primary, args.probe_mode, True)
-        if forced and primary == "repartition_stream":
+        m = measure(primary, args.probe_mode, True, keep=bool(args.dump_outputs))
+        if args.dump_outputs:
+            checkpoint_phase("dump outputs")
+            dump_device_table(m["held"], args.dump_outputs, "join" if world == 1 else f"join_rank{rank}", "l_orderkey", np_local)
+            m["held"].free()
+        if args.full and forced and primary == "repartition_stream":
             checkpoint(m, primary, "repartition")
             others["repartition"] = measure("repartition", args.probe_mode, True)
-    # secondary, outside the contract's timed region: the same step with the output in probe order
+    # secondary (--full), outside the contract's timed region: the same step with the output in probe order
     checkpoint(m, primary, "ordered_output")
-    ordered = measure(primary, 0, True) if (args.probe_mode == 3 and world == 1) else None
+    ordered = measure(primary, 0, True) if (args.full and args.probe_mode == 3 and world == 1) else None
     checkpoint_phase("done")
     line = make_line(m, primary, ordered, True) if rank == 0 else None
     orders.free()
@@ -662,21 +819,25 @@ def run_query(args, rank, world, dist):
     # DataFusion PhysicalPlan executed repeatedly would (`config.plan` says so; Q3's operators take their expressions per call)
     q1_plan = queries.plan_q1(lineitem, group) if args.workload == "q1" else None
 
-    def step():
+    def step(hold=False):
+        """(output rows, the output table when `hold`, else None: the caller frees it)"""
         out = queries.q1(lineitem, group, plan=q1_plan) if args.workload == "q1" else queries.q3(*tables, group=group)
         n = out.num_rows
-        out.free()
-        return n
+        if not hold:
+            out.free()
+        return n, (out if hold else None)
     checkpoint_phase(f"{args.workload} warm-up")
     for _ in range(args.warmup):
         step()
     checkpoint_phase(f"{args.workload} timed steps")
-    if args.workload == "q3":   # the intermediate row counts of the algorithmic-bytes table (8d config 5), outside the timed region
-        res = queries.q3(*tables, group=group, stats=q3_stats)
-    else:
-        res = queries.q1(lineitem, group, plan=q1_plan)
-    gpu_result = res.to_arrow()      # what the CPU leg's result is compared with (outside the timed region)
-    res.free()
+    gpu_result = None
+    if args.full:
+        if args.workload == "q3":   # the intermediate row counts of the algorithmic-bytes table (8d config 5), outside the timed region
+            res = queries.q3(*tables, group=group, stats=q3_stats)
+        else:
+            res = queries.q1(lineitem, group, plan=q1_plan)
+        gpu_result = res.to_arrow()      # what the CPU leg's result is compared with (outside the timed region)
+        res.free()
     comm = None
     if world > 1:
         from datafusion_amd.exchange import comm_for
@@ -685,15 +846,19 @@ def run_query(args, rank, world, dist):
     ops.profile_enable(True)
     ops.profile_reset()
     ops.metrics_reset()
-    dt, n_out = timed(step, args.steps, barrier)
+    dt, (n_out, held) = timed(step, args.steps, barrier)
     stats = ops.profile_stats()
     launch_recs = {k: ops.profile_launches(k) for k, v in stats.items() if v["calls"] > args.steps}
     alg_local = ops.metrics()["hbm_bytes_algorithmic"] // args.steps   # sum of the kernels' algorithmic bytes of one step, as the library counts them
     ops.profile_enable(False)
     xs = comm.stats(reset=True) if comm is not None else None
     dt, (rows, nbytes, alg_kernels) = max_over_ranks(dist, dt, rows_local, bytes_local, alg_local)
+    if args.dump_outputs:
+        checkpoint_phase("dump outputs")
+        dump_arrow(held.to_arrow(), args.dump_outputs, args.workload if world == 1 else f"{args.workload}_rank{rank}")
+    held.free()
     counts = None
-    if args.workload == "q3":
+    if args.workload == "q3" and args.full:
         counts = max_over_ranks(dist, 0.0, *(q3_stats.get(k, 0) for k in ("customer_filtered", "semi_join", "join", "groups")), *(t.num_rows for t in tables))[1]
     checkpoint_phase("done")
     if rank != 0:
@@ -705,9 +870,11 @@ def run_query(args, rank, world, dist):
     if args.workload == "q1":
         alg_table = [{"operator": "FilterExec + ProjectionExec + AggregateExec (fused node) over [l_shipdate, l_quantity, l_extendedprice, l_discount, l_tax, "
                                   "l_returnflag (u8), l_linestatus (u8)]", "input_bytes": rows * 70, "output_bytes": n_out * 10 * 16}]
-    else:
+    elif counts is not None:
         alg_table = q3_algorithmic_table(counts[4], counts[5], counts[6], dict(zip(("customer_filtered", "semi_join", "join", "groups"), counts[:4])))
-    alg = sum(r["input_bytes"] + r["output_bytes"] for r in alg_table)
+    else:
+        alg_table = None      # Q3's table needs the intermediate row counts of a run of its own (--full)
+    alg = sum(r["input_bytes"] + r["output_bytes"] for r in alg_table) if alg_table else None
     roof, roof_launches = None, None
     if top and top[0][1]["calls"]:
         name, d = top[0]
@@ -748,8 +915,9 @@ def run_query(args, rank, world, dist):
         # referenced column read once) is kept beside it under its own name and is NOT a roofline fraction
         "kernel_algorithmic_bytes_per_step": int(alg_kernels),
         "algorithmic_gb_per_s": round(alg_kernels / step_s / 1e9, 1), "hbm_frac_whole_step": round(alg_kernels / step_s / 1e9 / (HBM_PEAK_GBS * world), 4),
-        "survey_8d_formula": {"bytes_per_step": int(alg), "table": alg_table, "gb_per_s": round(alg / step_s / 1e9, 1),
-                              "note": "referenced input column bytes + output bytes per operator; not a roofline fraction when the plan skips columns of dropped rows"},
+        **({"survey_8d_formula": {"bytes_per_step": int(alg), "table": alg_table, "gb_per_s": round(alg / step_s / 1e9, 1),
+                                  "note": "referenced input column bytes + output bytes per operator; not a roofline fraction when the plan skips columns of dropped rows"}}
+           if alg_table else {}),
         "roofline": roof, **({"roofline_per_launch": roof_launches} if roof_launches else {}),
         "kernels": {k: {"calls": v["calls"], "avg_ms": round(v["total_ms"] / max(1, v["calls"]), 4)} for k, v in top},
         "kernel_ms_per_step": round(sum(v["total_ms"] for v in stats.values()) / args.steps, 4),
@@ -757,7 +925,7 @@ def run_query(args, rank, world, dist):
     }
     if counts is not None:
         line["config"]["intermediate_rows"] = dict(zip(("customer_filtered", "semi_join", "join", "groups"), counts[:4]))
-    if not args.no_cpu and world == 1:
+    if args.full and not args.no_cpu and world == 1:
         cb = cpu_baseline_query(args.workload, args.sf, os.cpu_count() or 1, device_tables=tables, max_sf=args.cpu_sf)
         cpu_result = cb.pop("result")
         if cb["same_workload_as_gpu_leg"]:
@@ -776,7 +944,7 @@ ALSO_DEFAULT = "q1:100,q3:300"   # BASELINE config 4 (TPC-H Q1 SF100) and config
 
 
 def also_legs(args, spec, deadline_s=900.0):
-    """BASELINE configs 4 and 5 beside the headline, on the default single-GPU line: each runs as its own process (`bench.py --workload q1 /
+    """BASELINE configs 4 and 5 beside the headline, on the single-GPU --full line: each runs as its own process (`bench.py --workload q1 /
     q3` at the configuration's scale factor, the same --steps / --warmup, its CPU leg included) AFTER the headline's timed region and after
     its tables are freed, and its line is folded into `also` — ms_per_step, rows/s, the dominant kernel's roofline, the whole-step
     fraction, the CPU leg on the same tables and whether the oracle's result equals the GPU leg's.  A leg that fails or runs out of time
@@ -789,7 +957,7 @@ def also_legs(args, spec, deadline_s=900.0):
         what = f"BASELINE config {4 if workload == 'q1' else 5}: TPC-H {workload.upper()} at SF{sf:g} on one GPU"
         left = deadline_s - (time.perf_counter() - t_start)
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--workload", workload, "--sf", str(sf), "--steps", str(args.steps),
-               "--warmup", str(args.warmup), "--no-also"] + (["--no-cpu"] if args.no_cpu else []) + ([] if args.cpu_sf is None else ["--cpu-sf", str(args.cpu_sf)])
+               "--warmup", str(args.warmup), "--no-also", "--full"] + (["--no-cpu"] if args.no_cpu else []) + ([] if args.cpu_sf is None else ["--cpu-sf", str(args.cpu_sf)])
         try:
             if left < 30:
                 raise TimeoutError("no time left for this leg")
@@ -850,18 +1018,29 @@ def main():
                     help="N > 1: seconds one phase (RCCL bootstrap, table generation, one exchange flavour's warm-up + timed steps) may take before rank 0 "
                          "prints the line of what HAS been measured with a `watchdog` object and every rank exits (0 = no watchdog)")
     ap.add_argument("--also", default=None,
-                    help=f"workload:SF pairs run after the headline and folded into `also` (default {ALSO_DEFAULT} when --sf is 100, nothing otherwise)")
+                    help=f"--full: workload:SF pairs run after the headline and folded into `also` (default {ALSO_DEFAULT} when --sf is 100, nothing otherwise)")
     ap.add_argument("--no-also", action="store_true",
-                    help="the default single-GPU join line also carries BASELINE configs 4 and 5 (Q1 SF100, Q3 SF300, each run as its own process after "
+                    help="the --full single-GPU join line also carries BASELINE configs 4 and 5 (Q1 SF100, Q3 SF300, each run as its own process after "
                          "the headline's timed region) under `also`; this leaves them out")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what takes runs of its own: the ordered_output step, the CPU baseline, `also`, the pruned exchange "
+                         "at N > 1, Q3's intermediate row counts and the oracle's check of the Q1 / Q3 result (off: only the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float64, at most 48 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload == "join" and (args.gpus > 1 or args.exchange != "auto") and args.exchange in ("auto", "repartition_stream"):
+        ap.error("--dump-outputs: the streamed hash exchange hands back no output table; name --exchange repartition, broadcast or pruned")
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_spawn(args))
     start_watchdog(args, int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")))
     rank, world, _local, dist = setup_dist(args)
     checkpoint_phase("generate tables")
     line = run_join(args, rank, world, dist) if args.workload == "join" else run_query(args, rank, world, dist)
-    also = "" if args.no_also else (args.also if args.also is not None else (ALSO_DEFAULT if args.sf == 100.0 else ""))
+    also = "" if (args.no_also or not args.full) else (args.also if args.also is not None else (ALSO_DEFAULT if args.sf == 100.0 else ""))
     if world == 1 and args.workload == "join" and args.exchange == "auto" and also:
         from datafusion_amd import _lib
         _lib.load().dfgpu_mem_trim()    # the headline's HBM goes back to the driver before the other configurations take theirs

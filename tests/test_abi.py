@@ -250,10 +250,11 @@ def test_rust_shim_binds_only_declared_entry_points_and_the_join_sequence_the_c_
 
 
 def test_rust_shim_targets_the_reference_workspace_versions():
-    """shim/Cargo.toml pins the datafusion / arrow versions of the reference workspace (skipped on the GPU box, where /root/reference does not exist)"""
-    ref = "/root/reference/Cargo.toml"
-    if not os.path.exists(ref):
-        pytest.skip("no reference checkout here")
+    """shim/Cargo.toml pins the datafusion / arrow versions of the reference workspace (a DataFusion checkout named by $DATAFUSION_REFERENCE;
+    skipped without one)"""
+    ref = os.path.join(os.environ.get("DATAFUSION_REFERENCE", ""), "Cargo.toml")
+    if not os.environ.get("DATAFUSION_REFERENCE") or not os.path.exists(ref):
+        pytest.skip("no reference checkout: set DATAFUSION_REFERENCE to a DataFusion checkout")
     text = open(ref).read()
     df = re.search(r'^version = "([0-9.]+)"', text[text.index("[workspace.package]"):], flags=re.M).group(1)
     arrow = re.search(r'^arrow = \{ version = "([0-9.]+)"', text, flags=re.M).group(1)

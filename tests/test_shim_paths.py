@@ -5,14 +5,14 @@ a renamed type, a moved module or a typo would otherwise only show when a mainta
 Resolution is lexical: the umbrella crate's re-exports (datafusion/core/src/lib.rs:798-890: `pub mod physical_plan { pub use
 datafusion_physical_plan::*; }` ...) map the first path segment to the source directories of the crates behind it; the module
 segments must exist there as files / directories / `pub mod` declarations; the item must be declared `pub` (struct / enum /
-trait / fn / type / const / static / mod / macro) or re-exported with `pub use` somewhere in those crates.  Skipped where
-/root/reference is absent (the GPU box)."""
+trait / fn / type / const / static / mod / macro) or re-exported with `pub use` somewhere in those crates.  The reference is the
+DataFusion checkout named by $DATAFUSION_REFERENCE; skipped without one."""
 import os
 import re
 
 import pytest
 
-REF = "/root/reference/datafusion"
+REF = os.path.join(os.environ["DATAFUSION_REFERENCE"], "datafusion") if os.environ.get("DATAFUSION_REFERENCE") else ""
 SHIM = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "shim", "src")
 
 # first segment after `datafusion::` -> crate source directories that may hold the item (the alias's crate first, then what it re-exports)
@@ -32,7 +32,7 @@ CRATES = {
     "scalar": ["common/src"],
     "prelude": ["core/src"],
 }
-EXTERNAL = {"arrow", "parquet", "object_store"}   # third-party crates re-exported by the umbrella crate: not in /root/reference
+EXTERNAL = {"arrow", "parquet", "object_store"}   # third-party crates re-exported by the umbrella crate: not in the reference checkout
 
 
 def _imports():
@@ -112,7 +112,7 @@ def _module_exists(mod, dirs):
     return False
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference checkout is not present on this machine")
+@pytest.mark.skipif(not REF or not os.path.isdir(REF), reason="no reference checkout: set DATAFUSION_REFERENCE to a DataFusion checkout")
 def test_every_datafusion_item_the_shim_imports_is_public_in_the_reference():
     imports = _imports()
     assert len(imports) > 60, "the shim's imports were not found"
