@@ -723,14 +723,15 @@ __global__ __launch_bounds__(BLOCK) void k_emit_avg(int is_decimal, const unsign
 // WORD (a wave's ballot: no byte-per-row detour) and the column's count of valid rows — read back once for all columns, together
 // with the AVG overflow flags.  stats[2 e] = valid rows of entry e, stats[2 e + 1] = overflow seen.
 struct EmitEntry {
-  int kind;                         // 0 = accumulator value (mode as k_emit_values), 1 = AVG (mode = is_decimal)
+  int kind;                         // 0 = accumulator value (mode as k_emit_values), 1 = AVG (mode = is_decimal), 2 = VAR / STDDEV (mode: VarEmit bits)
   int mode;
-  const unsigned long long *lo, *hi, *cnt;
+  const unsigned long long *lo, *hi, *cnt;   // VAR / STDDEV: hi = m2, cnt = count
   const uint32_t* seen;             // null: every row is valid
   unsigned long long mul_lo, mul_hi;   // AVG over decimals: 10^(return scale - sum scale)
   void* dst;
   uint64_t* valid_words;            // null: the column is not nullable
 };
+enum VarEmit : int { VAR_SAMPLE = 1, VAR_SQRT = 2 };
 constexpr int EMIT_MAX = 2 * MAX_AGGS;
 struct EmitSet {
   int n;
@@ -744,8 +745,8 @@ __global__ __launch_bounds__(BLOCK) void k_emit_set(EmitSet s, int64_t n, unsign
   const unsigned lane = lane_id();
   const int64_t n_words = (n + WAVE - 1) / WAVE;
   const int64_t wv = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * BLOCK) >> 6;
-  const bool avg = e.kind != 0;
-  const bool need_lo = avg || e.mode != 5, need_hi = avg ? e.mode != 0 : e.mode == 1;
+  const bool avg = e.kind == 1, var = e.kind == 2, counted = avg || var;
+  const bool need_lo = avg || (!var && e.mode != 5), need_hi = var || (avg ? e.mode != 0 : e.mode == 1);
   unsigned long long valid_rows = 0;
   bool overflow = false;
   for (int64_t w0 = wv * U; w0 < n_words; w0 += n_waves * U) {
@@ -756,7 +757,7 @@ __global__ __launch_bounds__(BLOCK) void k_emit_set(EmitSet s, int64_t n, unsign
     for (int u = 0; u < U; u++) {
       const int64_t i = ((w0 + u) << 6) + lane;
       in[u] = i < n;
-      sn[u] = in[u] && !avg && e.seen ? e.seen[i] : 1u;
+      sn[u] = in[u] && !counted && e.seen ? e.seen[i] : 1u;
     }
 #pragma unroll
     for (int u = 0; u < U; u++) {
@@ -767,14 +768,21 @@ __global__ __launch_bounds__(BLOCK) void k_emit_set(EmitSet s, int64_t n, unsign
     for (int u = 0; u < U; u++) {
       const int64_t i = ((w0 + u) << 6) + lane;
       hi[u] = in[u] && need_hi ? e.hi[i] : 0ull;
-      cn[u] = in[u] && avg ? e.cnt[i] : 0ull;
+      cn[u] = in[u] && counted ? e.cnt[i] : 0ull;
     }
 #pragma unroll
     for (int u = 0; u < U; u++) {
       const int64_t i = ((w0 + u) << 6) + lane;
       bool ok = false;
       if (in[u]) {
-        if (!avg) {
+        if (var) {
+          // variance.rs evaluate: m2 / (n - 1) or m2 / n; NULL below two (sample) or one (population) values
+          const unsigned long long c = cn[u];
+          ok = c > ((e.mode & VAR_SAMPLE) ? 1ull : 0ull);
+          double v = ok ? __longlong_as_double((long long)hi[u]) / (double)((e.mode & VAR_SAMPLE) ? c - 1 : c) : 0.0;
+          if (e.mode & VAR_SQRT) v = sqrt(v);
+          ((double*)e.dst)[i] = v;
+        } else if (!avg) {
           ok = sn[u] != 0;
           switch (e.mode) {
             case 0: ((unsigned long long*)e.dst)[i] = ok ? lo[u] : 0ull; break;
@@ -817,6 +825,118 @@ __global__ __launch_bounds__(BLOCK) void k_emit_set(EmitSet s, int64_t n, unsign
     if (t) atomicAdd(&stats[2 * blockIdx.y], t);
   }
   if (overflow) stats[2 * blockIdx.y + 1] = 1ull;
+}
+
+// ------------------------------------------------------------------- VAR / STDDEV
+// Per-group (count, mean, m2) state of variance.rs.  An update accumulates the batch's count and sum per group with the ordinary cells
+// (pass 1), turns the sum into the batch mean (k_var_center), sums the squared deviations from that mean (pass 2: k_var_m2) and merges
+// (n_b, mean_b, m2_b) into the running state (k_var_merge) — Chan's pairwise formula, VarianceGroupsAccumulator::merge.  The
+// deviations are taken about a mean of the same rows, so there is no Σx² - (Σx)²/n cancellation.  Final modes read partial states:
+// pass 1 sums nᵢ and nᵢ·meanᵢ, pass 2 sums m2ᵢ + nᵢ·(meanᵢ - mean)², which is what any order of pairwise merges gives.
+struct VarAcc {
+  const void* x;                    // raw modes: the argument; final modes: the partial means (Float64)
+  const uint64_t* valid;            // raw modes: the argument's validity (null: no NULLs)
+  int val;                          // VAL_F64 / VAL_I32_TO_F64 / VAL_I64_TO_F64
+  const unsigned long long* n_in;   // final modes: the partial counts, 0 where a row is skipped (k_var_weight); null in raw modes
+  const double* m2_in;              // final modes: the partial m2
+  unsigned long long* bn;           // [G] this batch: count
+  double* bmean;                    // [G] this batch: sum, then mean (k_var_center)
+  double* bm2;                      // [G] this batch: m2
+  unsigned long long* cnt;          // [G] the node's state
+  double* mean;
+  double* m2;
+};
+struct VarSet {
+  VarAcc a[MAX_AGGS];
+  int n;
+};
+// final modes: the count a partial row brings (0 = skipped: a NULL state column or an empty partial group) and count · mean
+__global__ __launch_bounds__(BLOCK) void k_var_weight(const unsigned long long* __restrict__ n_in, const uint64_t* __restrict__ n_valid, const double* __restrict__ mean_in,
+                                                      const uint64_t* __restrict__ mean_valid, const uint64_t* __restrict__ m2_valid, int64_t n,
+                                                      unsigned long long* __restrict__ n_out, double* __restrict__ w_out) {
+  for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
+    const bool ok = (!n_valid || bit_at(n_valid, i)) && (!mean_valid || bit_at(mean_valid, i)) && (!m2_valid || bit_at(m2_valid, i));
+    const unsigned long long c = ok ? n_in[i] : 0ull;
+    n_out[i] = c;
+    w_out[i] = c ? (double)c * mean_in[i] : 0.0;
+  }
+}
+__global__ __launch_bounds__(BLOCK) void k_var_center(VarSet s, int64_t G) {
+  for (int64_t g = (int64_t)blockIdx.x * BLOCK + threadIdx.x; g < G; g += (int64_t)gridDim.x * BLOCK)
+    for (int k = 0; k < s.n; k++) {
+      const unsigned long long c = s.a[k].bn[g];
+      if (c) s.a[k].bmean[g] = s.a[k].bmean[g] / (double)c;
+    }
+}
+// what row i adds to its group's m2 (false: nothing, a NULL argument or a skipped partial row)
+__device__ __forceinline__ bool var_term(const VarAcc& v, int64_t i, uint32_t gid, double& t) {
+  if (v.n_in) {
+    const unsigned long long c = v.n_in[i];
+    if (!c) return false;
+    const double d = ((const double*)v.x)[i] - v.bmean[gid];
+    t = v.m2_in[i] + (double)c * d * d;
+    return true;
+  }
+  if (v.valid && !bit_at(v.valid, i)) return false;
+  double x;
+  switch (v.val) {
+    case VAL_I32_TO_F64: x = (double)((const int32_t*)v.x)[i]; break;
+    case VAL_I64_TO_F64: x = (double)((const int64_t*)v.x)[i]; break;
+    default: x = ((const double*)v.x)[i]; break;
+  }
+  const double d = x - v.bmean[gid];
+  t = d * d;
+  return true;
+}
+// pass 2, as k_accumulate_lds / k_accumulate_global: LDS replicas of the m2 cells when every (aggregate, group) fits, f64 atomics in HBM otherwise
+template <bool USE_LDS>
+__global__ __launch_bounds__(BLOCK) void k_var_m2(InternCtx c, const uint32_t* __restrict__ slot_gid, int has_groups, int64_t row_offset, int64_t n, VarSet s,
+                                                  int ngroups, int nrep) {
+  __shared__ double s_m2[USE_LDS ? LDS_CELLS : 1];
+  const int per_rep = s.n * ngroups;
+  if (USE_LDS) {
+    for (int x = threadIdx.x; x < per_rep * nrep; x += BLOCK) s_m2[x] = 0.0;
+    __syncthreads();
+  }
+  const int rep = (int)(threadIdx.x % (unsigned)nrep);
+  for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
+    const uint32_t gid = has_groups ? lookup_gid(c, slot_gid, row_offset + i) : 0u;
+    for (int k = 0; k < s.n; k++) {
+      double t;
+      if (!var_term(s.a[k], i, gid, t)) continue;
+      if (USE_LDS) atomicAdd(&s_m2[rep * per_rep + k * ngroups + (int)gid], t);
+      else atomicAdd(&s.a[k].bm2[gid], t);
+    }
+  }
+  if (USE_LDS) {
+    __syncthreads();
+    for (int x = threadIdx.x; x < per_rep; x += BLOCK) {
+      double t = 0.0;
+      for (int r = 0; r < nrep; r++) t += s_m2[r * per_rep + x];
+      atomicAdd(&s.a[x / ngroups].bm2[x % ngroups], t);
+    }
+  }
+}
+// (n_b, mean_b, m2_b) of this batch into the node's (cnt, mean, m2): VarianceGroupsAccumulator::merge (variance.rs)
+__global__ __launch_bounds__(BLOCK) void k_var_merge(VarSet s, int64_t G) {
+  for (int64_t g = (int64_t)blockIdx.x * BLOCK + threadIdx.x; g < G; g += (int64_t)gridDim.x * BLOCK)
+    for (int k = 0; k < s.n; k++) {
+      const VarAcc& v = s.a[k];
+      const unsigned long long nb = v.bn[g];
+      if (!nb) continue;
+      const unsigned long long na = v.cnt[g];
+      const double mb = v.bmean[g], m2b = v.bm2[g];
+      if (!na) {
+        v.cnt[g] = nb;
+        v.mean[g] = mb;
+        v.m2[g] = m2b;
+        continue;
+      }
+      const double ma = v.mean[g], fa = (double)na, fb = (double)nb, nt = fa + fb, d = ma - mb;
+      v.cnt[g] = na + nb;
+      v.mean[g] = ma * fa / nt + mb * fb / nt;
+      v.m2[g] = v.m2[g] + m2b + d * d * fa * fb / nt;
+    }
 }
 
 // ------------------------------------------------------------------------------- host
@@ -939,8 +1059,20 @@ struct AccPlan {
   int kind, val;
   bool needs_hi;
 };
+static bool is_variance(int func) { return func >= DFGPU_AGG_VAR_SAMP && func <= DFGPU_AGG_STDDEV_POP; }
 static AccPlan plan_for(int func, const dfgpu_field& t, bool merging_counts) {
   switch (func) {
+    case DFGPU_AGG_VAR_SAMP:
+    case DFGPU_AGG_VAR_POP:
+    case DFGPU_AGG_STDDEV_SAMP:
+    case DFGPU_AGG_STDDEV_POP:
+      // lo = mean, hi = m2 (f64 bits), cnt = count; integers are converted as AVG converts them.  In final modes t is the mean's type
+      switch (t.type) {
+        case DFGPU_FLOAT64: return {ACC_SUM_F64, VAL_F64, true};
+        case DFGPU_INT32: return {ACC_SUM_F64, VAL_I32_TO_F64, true};
+        case DFGPU_INT64: return {ACC_SUM_F64, VAL_I64_TO_F64, true};
+      }
+      throw Error("VAR/STDDEV over " + type_name(t) + " is not supported on the GPU path (the planner casts the argument to Float64)");
     case DFGPU_AGG_COUNT:
       // Final modes merge partial counts by summing them (count.rs merge_batch)
       if (merging_counts) return {ACC_SUM_I64, t.type == DFGPU_UINT64 ? VAL_U64 : VAL_I64, false};
@@ -1701,7 +1833,7 @@ static std::vector<AccPlan> grow_accumulators(Aggregate& A, int64_t G0, int64_t 
       fresh(a.lo, acc_identity(p.kind), 8);
       if (p.needs_hi) fresh(a.hi, 0ull, 8);
       fresh(a.seen, 0ull, 4);
-      if (a.func == DFGPU_AGG_AVG) fresh(a.cnt, 0ull, 8);
+      if (a.func == DFGPU_AGG_AVG || is_variance(a.func)) fresh(a.cnt, 0ull, 8);
       plans.push_back(p);
     }
     if (m) {
@@ -1715,7 +1847,7 @@ static std::vector<AccPlan> grow_accumulators(Aggregate& A, int64_t G0, int64_t 
     a.lo = grown(a.lo, G0, G1, acc_identity(p.kind), 8, init);
     if (p.needs_hi) a.hi = grown(a.hi, G0, G1, 0ull, 8, init);
     a.seen = grown(a.seen, G0, G1, 0, 4, init);
-    if (a.func == DFGPU_AGG_AVG) a.cnt = grown(a.cnt, G0, G1, 0ull, 8, init);
+    if (a.func == DFGPU_AGG_AVG || is_variance(a.func)) a.cnt = grown(a.cnt, G0, G1, 0ull, 8, init);
     plans.push_back(p);
   }
   return plans;
@@ -4166,6 +4298,11 @@ static bool agg_update_fused(Aggregate& A, const Table& in, const dfgpu_expr* pr
     return false;
   }
   for (const AggState& a : A.aggs)
+    if (is_variance(a.func)) {
+      why = "VAR/STDDEV need a second pass over the batch";
+      return false;
+    }
+  for (const AggState& a : A.aggs)
     if (a.has_arg && (a.func == DFGPU_AGG_MIN || a.func == DFGPU_AGG_MAX)) {
       dfgpu_expr e{a.nodes.data(), (int)a.nodes.size(), a.root};
       if (wide_minmax(a.func, expr_type(e, in))) {
@@ -4398,14 +4535,15 @@ static void agg_update_unfused(Aggregate& A, const Table& in) {
     key_cols.back().name = A.group_names[g];
   }
   // argument / state columns per aggregate
-  struct Inputs { Column v; Column c; bool has_v = false, has_c = false; };
+  struct Inputs { Column v; Column c; Column m2; bool has_v = false, has_c = false; };
   std::vector<Inputs> inputs(A.aggs.size());
   int state_col = ngk;
   for (size_t k = 0; k < A.aggs.size(); k++) {
     AggState& a = A.aggs[k];
     if (final_mode) {
-      // partial-state schema: AVG -> [count, sum]; others -> one column (average.rs:317-360, sum.rs:281-301)
-      if (a.func == DFGPU_AGG_AVG) {
+      // partial-state schema: AVG -> [count, sum]; VAR / STDDEV -> [count, mean, m2]; others -> one column (average.rs:317-360,
+      // sum.rs:281-301, variance.rs)
+      if (a.func == DFGPU_AGG_AVG || is_variance(a.func)) {
         DFGPU_CHECK(state_col + 1 < (int)in.cols.size(), "final aggregate input has too few state columns");
         inputs[k].c = in.cols[state_col++];
         inputs[k].has_c = true;
@@ -4413,6 +4551,12 @@ static void agg_update_unfused(Aggregate& A, const Table& in) {
       DFGPU_CHECK(state_col < (int)in.cols.size(), "final aggregate input has too few state columns");
       inputs[k].v = in.cols[state_col++];
       inputs[k].has_v = true;
+      if (is_variance(a.func)) {
+        DFGPU_CHECK(state_col < (int)in.cols.size(), "final aggregate input has too few state columns");
+        inputs[k].m2 = in.cols[state_col++];
+        DFGPU_CHECK(inputs[k].c.field.type == DFGPU_UINT64 && inputs[k].v.field.type == DFGPU_FLOAT64 && inputs[k].m2.field.type == DFGPU_FLOAT64,
+                    "VAR/STDDEV partial state must be [count UInt64, mean Float64, m2 Float64]");
+      }
     } else if (a.has_arg) {
       dfgpu_expr e{a.nodes.data(), (int)a.nodes.size(), a.root};
       inputs[k].v = datum_to_column(evaluate(e, in), n, a.name);
@@ -4441,9 +4585,56 @@ static void agg_update_unfused(Aggregate& A, const Table& in) {
   // ---- grow accumulators to G1 groups
   std::vector<AccPlan> plans = grow_accumulators(A, G0, G1);
   AccSet accs{};
+  VarSet vars{};
+  std::vector<BufPtr> var_bufs;   // this batch's per-group count / sum / m2 of the VAR / STDDEV aggregates, final modes' weighted rows
   for (size_t k = 0; k < A.aggs.size(); k++) {
     AggState& a = A.aggs[k];
     const AccPlan& p = plans[k];
+    if (is_variance(a.func)) {
+      // pass 1 counts and sums this batch's values per group into fresh cells; pass 2 and the merge follow the accumulation below
+      if (n == 0) continue;
+      VarAcc v{};
+      for (int b = 0; b < 3; b++) var_bufs.push_back(make_zero_buf((size_t)G1 * 8));
+      v.bn = var_bufs[var_bufs.size() - 3]->as<unsigned long long>();
+      v.bmean = var_bufs[var_bufs.size() - 2]->as<double>();
+      v.bm2 = var_bufs[var_bufs.size() - 1]->as<double>();
+      v.cnt = a.cnt->as<unsigned long long>();
+      v.mean = a.lo->as<double>();
+      v.m2 = a.hi->as<double>();
+      v.x = inputs[k].v.ptr();
+      AccDesc c{}, d{};
+      c.acc_lo = v.bn;
+      c.values = d.values = v.x;
+      d.acc_lo = reinterpret_cast<unsigned long long*>(v.bmean);
+      d.kind = ACC_SUM_F64;
+      if (final_mode) {
+        BufPtr nb = make_buf((size_t)n * 8), wb = make_buf((size_t)n * 8);
+        var_bufs.push_back(nb);
+        var_bufs.push_back(wb);
+        k_var_weight<<<grid_for(n, BLOCK), BLOCK, 0, r.stream>>>((const unsigned long long*)inputs[k].c.ptr(), inputs[k].c.valid_words(), (const double*)v.x,
+                                                                 inputs[k].v.valid_words(), inputs[k].m2.valid_words(), n, nb->as<unsigned long long>(), wb->as<double>());
+        DFGPU_HIP(hipGetLastError());
+        v.val = VAL_F64;
+        v.n_in = nb->as<unsigned long long>();
+        v.m2_in = (const double*)inputs[k].m2.ptr();
+        c.kind = ACC_SUM_I64;
+        c.val = VAL_U64;
+        c.values = v.n_in;
+        d.val = VAL_F64;
+        d.values = wb->ptr;
+      } else {
+        v.val = p.val;
+        v.valid = inputs[k].v.valid_words();
+        c.kind = ACC_COUNT;
+        c.val = d.val = p.val;
+        c.valid = d.valid = v.valid;
+      }
+      DFGPU_CHECK(accs.n + 2 <= MAX_AGGS, "too many aggregates for one GPU aggregate node");
+      accs.a[accs.n++] = c;
+      accs.a[accs.n++] = d;
+      vars.a[vars.n++] = v;
+      continue;
+    }
     AccDesc d{};
     d.kind = (a.func == DFGPU_AGG_COUNT && !a.has_arg && !final_mode) ? ACC_COUNT_STAR : p.kind;
     d.val = p.val;
@@ -4498,6 +4689,25 @@ static void agg_update_unfused(Aggregate& A, const Table& in) {
     k_accumulate_global<<<grid_for(n, BLOCK), BLOCK, 0, r.stream>>>(ictx, sg, ngk > 0, G0, n, accs);
   }
   DFGPU_HIP(hipGetLastError());
+  if (vars.n > 0) {
+    // VAR / STDDEV: the batch's means, the squared deviations from them (a second read of the argument), the merge into the state
+    k_var_center<<<grid_for(G1, BLOCK), BLOCK, 0, r.stream>>>(vars, G1);
+    DFGPU_HIP(hipGetLastError());
+    {
+      ProfileScope ps("agg_var_m2", n * 8 * vars.n * (final_mode ? 3 : 1));
+      if (G1 * vars.n <= LDS_CELLS) {
+        const int nrep = std::max(1, std::min(64, LDS_CELLS / (int)(G1 * vars.n)));
+        int p2 = 1;
+        while (p2 * 2 <= nrep) p2 *= 2;
+        k_var_m2<true><<<grid_for(n, BLOCK * 8), BLOCK, 0, r.stream>>>(ictx, sg, ngk > 0, G0, n, vars, (int)G1, p2);
+      } else {
+        k_var_m2<false><<<grid_for(n, BLOCK), BLOCK, 0, r.stream>>>(ictx, sg, ngk > 0, G0, n, vars, (int)G1, 1);
+      }
+      DFGPU_HIP(hipGetLastError());
+    }
+    k_var_merge<<<grid_for(G1, BLOCK), BLOCK, 0, r.stream>>>(vars, G1);
+    DFGPU_HIP(hipGetLastError());
+  }
   A.ngroups = G1;
   DFGPU_HIP(hipStreamSynchronize(r.stream));  // temporaries (evaluated columns, tables) are released on return
 }
@@ -4676,6 +4886,19 @@ static Table agg_emit(Aggregate& A) {
     else if (p.val == VAL_F64_ORDERED) mode = 2;
     else if (vf.type == DFGPU_INT32 || vf.type == DFGPU_DATE32) mode = 3;
     else if (vf.type == DFGPU_UINT8) mode = 4;
+    if (is_variance(a.func)) {
+      if (A.partial_out()) {
+        // state_fields of VAR / STDDEV: [count: UInt64, mean: Float64, m2: Float64] (variance.rs), an empty group's mean and m2 are 0
+        emit_later(fld(DFGPU_UINT64), a.name + "[count]", 0, 0, a.cnt, nullptr, nullptr, nullptr, 1, false);
+        emit_later(fld(DFGPU_FLOAT64), a.name + "[mean]", 0, 0, a.lo, nullptr, nullptr, nullptr, 1, false);
+        emit_later(fld(DFGPU_FLOAT64), a.name + "[m2]", 0, 0, a.hi, nullptr, nullptr, nullptr, 1, false);
+      } else {
+        const int vmode = (a.func == DFGPU_AGG_VAR_SAMP || a.func == DFGPU_AGG_STDDEV_SAMP ? VAR_SAMPLE : 0) |
+                          (a.func == DFGPU_AGG_STDDEV_SAMP || a.func == DFGPU_AGG_STDDEV_POP ? VAR_SQRT : 0);
+        emit_later(fld(DFGPU_FLOAT64), a.name, 2, vmode, nullptr, a.hi, nullptr, a.cnt, 1, true);
+      }
+      continue;
+    }
     if (a.func == DFGPU_AGG_AVG) {
       if (A.partial_out()) {
         // state_fields of AVG: [count: UInt64, sum] (average.rs:317-360)
@@ -4796,7 +5019,7 @@ int dfgpu_agg_create(int mode, const dfgpu_expr* group_by, const char* const* gr
     for (int k = 0; k < n_aggs; k++) {
       AggState a;
       a.func = aggs[k].func;
-      DFGPU_CHECK(a.func >= DFGPU_AGG_SUM && a.func <= DFGPU_AGG_AVG, "unsupported aggregate function");
+      DFGPU_CHECK(a.func >= DFGPU_AGG_SUM && a.func <= DFGPU_AGG_STDDEV_POP, "unsupported aggregate function");
       a.has_arg = aggs[k].has_arg != 0;
       DFGPU_CHECK(a.has_arg || a.func == DFGPU_AGG_COUNT, "only COUNT may omit its argument");
       if (a.has_arg && aggs[k].arg.nodes) {

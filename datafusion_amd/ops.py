@@ -16,7 +16,10 @@ JOIN_TYPES = {"Inner": 0, "Left": 1, "Right": 2, "Full": 3, "LeftSemi": 4, "Righ
               "RightAnti": 7, "LeftMark": 8, "RightMark": 9}
 NULL_EQUALITY = {"NullEqualsNothing": 0, "NullEqualsNull": 1}
 AGG_MODES = {"Partial": 0, "Final": 1, "FinalPartitioned": 2, "Single": 3, "SinglePartitioned": 4, "PartialReduce": 5}
-AGG_FUNCS = {"sum": 0, "min": 1, "max": 2, "count": 3, "avg": 4}
+AGG_FUNCS = {"sum": 0, "min": 1, "max": 2, "count": 3, "avg": 4, "var": 5, "var_pop": 6, "stddev": 7, "stddev_pop": 8,
+             # the aliases the reference registers (functions-aggregate/src/variance.rs, stddev.rs)
+             "var_samp": 5, "var_sample": 5, "var_population": 6, "stddev_samp": 7}
+VARIANCE_FUNCS = frozenset(f for f, i in AGG_FUNCS.items() if i >= 5)
 GPU_MIN_KEY_DENSITY = 1.0 / 64.0      # DFGPU_DEFAULT_MIN_KEY_DENSITY (include/dfgpu.h); the reference's CPU default is 0.15
 TABLE_MODES = {"auto": 0, "hash_map": 1, "array_map": 2, "rank_map": 3}
 PROBE_MODES = {"auto": 0, "two_pass": 1, "single_pass_ordered": 2, "single_pass_unordered": 3, "order_not_needed": 4}

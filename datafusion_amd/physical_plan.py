@@ -766,7 +766,9 @@ def plan_schema(node):
             for func, e, n in node.aggr_expr:
                 t = None if e is None else ops.expr_type(empty, e)
                 if node.mode == "Partial":      # state fields (sum.rs:281-301, average.rs:317-360, count.rs): AVG = count + sum
-                    if func == "avg":
+                    if func in ops.VARIANCE_FUNCS:   # variance.rs state_fields: count, mean, m2
+                        fields += [pa.field(n + "[count]", pa.uint64()), pa.field(n + "[mean]", pa.float64()), pa.field(n + "[m2]", pa.float64())]
+                    elif func == "avg":
                         fields.append(pa.field(n + "[count]", pa.uint64()))
                         # avg_sum_data_type (average.rs:131-172): the input precision + 13 digits, never narrower than Decimal128's 38
                         fields.append(pa.field(n + "[sum]", pa.decimal128(38, t.scale) if pa.types.is_decimal128(t) else pa.float64()))
@@ -799,6 +801,8 @@ def _agg_type(func, t):
         return _sum_type(t)
     if func == "avg":
         return pa.decimal128(min(38, t.precision + 4), min(38, t.scale + 4)) if pa.types.is_decimal128(t) else pa.float64()   # average.rs:219-252
+    if func in ops.VARIANCE_FUNCS:
+        return pa.float64()     # variance.rs / stddev.rs return_type
     return t    # min / max
 
 
@@ -843,6 +847,9 @@ def unsupported_reason(node):
                     # aggregate.hip wide_minmax_values_fit: the device compares 64-bit words; values beyond them are only found at run time
                     return f"{func.upper()}({n}) over {t}: values of more than 18 digits do not fit the device's 64-bit comparison"
                 if func in ("sum", "avg", "min", "max") and (pa.types.is_boolean(t) or pa.types.is_string(t) or pa.types.is_large_string(t)):
+                    return f"{func.upper()}({n}) over {t} is not supported on the GPU path"
+                if func in ops.VARIANCE_FUNCS and t not in (pa.float64(), pa.int32(), pa.int64()):
+                    # aggregate.hip plan_for: the device reads a Float64, Int32 or Int64 argument (the planner casts to Float64)
                     return f"{func.upper()}({n}) over {t} is not supported on the GPU path"
         finally:
             empty.free()

@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define DFGPU_ABI_VERSION 13
+#define DFGPU_ABI_VERSION 14
 
 /* Arrow C Data Interface (https://arrow.apache.org/docs/format/CDataInterface.html) */
 #ifndef ARROW_C_DATA_INTERFACE
@@ -559,7 +559,12 @@ typedef enum dfgpu_agg_mode {
   DFGPU_AGG_SINGLE_PARTITIONED = 4,
   DFGPU_AGG_PARTIAL_REDUCE = 5    /* partial state -> partial state: merges like Final, emits like Partial (mod.rs:340-361) */
 } dfgpu_agg_mode;
-typedef enum dfgpu_agg_func { DFGPU_AGG_SUM = 0, DFGPU_AGG_MIN = 1, DFGPU_AGG_MAX = 2, DFGPU_AGG_COUNT = 3, DFGPU_AGG_AVG = 4 } dfgpu_agg_func;
+/* VAR_SAMP .. STDDEV_POP (ABI 14): variance.rs / stddev.rs — registered names var, var_pop, stddev, stddev_pop; the argument is
+ * Float64, Int32 or Int64 (the planner casts it to Float64), the result Float64 */
+typedef enum dfgpu_agg_func {
+  DFGPU_AGG_SUM = 0, DFGPU_AGG_MIN = 1, DFGPU_AGG_MAX = 2, DFGPU_AGG_COUNT = 3, DFGPU_AGG_AVG = 4,
+  DFGPU_AGG_VAR_SAMP = 5, DFGPU_AGG_VAR_POP = 6, DFGPU_AGG_STDDEV_SAMP = 7, DFGPU_AGG_STDDEV_POP = 8
+} dfgpu_agg_func;
 typedef struct dfgpu_agg_spec {
   int32_t func;          /* dfgpu_agg_func */
   int32_t has_arg;       /* 0 = COUNT(*) */
@@ -575,7 +580,8 @@ typedef struct dfgpu_agg_spec {
  * (GroupValues group_values/mod.rs:93, GroupsAccumulator expr-common/src/
  * groups_accumulator.rs:105).  In FINAL modes the input is the partial-state schema the
  * reference uses (group cols, then per aggregate: SUM -> [sum]; COUNT -> [count];
- * MIN/MAX -> [value]; AVG -> [count u64, sum]; sum.rs:281-301, average.rs:317-360) and
+ * MIN/MAX -> [value]; AVG -> [count u64, sum]; sum.rs:281-301, average.rs:317-360; VAR_* / STDDEV_* -> [count u64,
+ * mean f64, m2 f64], m2 = the sum of squared deviations from the mean, variance.rs VarianceGroupsAccumulator::state) and
  * `arg`/`group_by` expressions are ignored beyond their count. */
 int dfgpu_agg_create(int mode, const dfgpu_expr* group_by, const char* const* group_names, int n_group,
                      const dfgpu_agg_spec* aggs, int n_aggs, dfgpu_agg_t* out);

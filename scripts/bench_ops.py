@@ -8,6 +8,7 @@ does not cover (bench.py = config 3, the Q3 hash join):
   config 5  TPC-H Q3 end to end (the reference's physical plan), one GPU
   K10       RepartitionExec(Hash) of the Q3 lineitem projection into 8 partitions
   K11/K12   SortExec of orders by (o_orderdate, o_orderkey) and TopK(10)
+  agg_var   VAR / STDDEV beside AVG / SUM in the same node shapes (Q1's keys over Float64 money; GROUP BY o_custkey)
 
 For every case: rows/s over the input rows, algorithmic GB/s (referenced input columns read once
 + output written once, per §8d) over the wall time of the device region (inputs resident in HBM,
@@ -193,6 +194,38 @@ def main():
                     note="bytes = 2*N*40 (every column read once, written once)")
             t.free()
         li.free()
+        ops.sync()
+
+    # ------------------------------------------------------------------ VAR / STDDEV beside AVG / SUM over the same node shapes
+    if want("agg_var"):
+        # bytes: keys and argument read once, state or result written once.  The variance legs read the argument twice (their second
+        # pass is the floor of the cost); that second read is not counted, so their fraction of peak is comparable with the companion's
+        li = ops.tpch_lineitem(args.sf, float_money=True)
+        t = li.select(["l_returnflag", "l_linestatus", "l_extendedprice", "l_quantity"])
+        li.free()
+        n = t.num_rows
+        gb = [(col("l_returnflag"), "l_returnflag"), (col("l_linestatus"), "l_linestatus")]
+        legs = [("AVG(l_extendedprice), AVG(l_quantity)", [("avg", col("l_extendedprice"), "a"), ("avg", col("l_quantity"), "b")]),
+                ("STDDEV(l_extendedprice), VAR_POP(l_quantity)", [("stddev", col("l_extendedprice"), "a"), ("var_pop", col("l_quantity"), "b")])]
+        for label, aggs in legs:
+            measure(f"GROUP BY l_returnflag, l_linestatus {label} SF{args.sf:g} (Float64 money)", lambda aggs=aggs: ops.aggregate(t, gb, aggs, "Single"), n, n * 18,
+                    note="bytes = N*(1+1+8+8) in; 4 groups out")
+        results[-1]["ratio_to_avg"] = round(results[-1]["ms"] / results[-2]["ms"], 2)
+        t.free()
+        oc = ops.tpch_orders(args.sf).select(["o_custkey", "o_orderkey"])
+        holder = {}
+        legs = [("COUNT(*), SUM(o_orderkey)", [("count", None, "n"), ("sum", col("o_orderkey"), "s")], 16),
+                ("VAR(o_orderkey)", [("var", col("o_orderkey"), "v")], 8)]
+        for label, aggs, out_w in legs:
+            def run_v(aggs=aggs):
+                o = ops.aggregate(oc, [(col("o_custkey"), "o_custkey")], aggs, "Single")
+                holder["g"] = o.num_rows
+                return o
+            measure(f"GROUP BY o_custkey {label} SF{args.sf:g}", run_v, oc.num_rows, lambda out_w=out_w: oc.num_rows * 16 + holder["g"] * (8 + out_w),
+                    note=f"bytes = N*(8+8) in + groups*(8+{out_w}) out")
+            results[-1]["groups"] = holder["g"]
+        results[-1]["ratio_to_sum"] = round(results[-1]["ms"] / results[-2]["ms"], 2)
+        oc.free()
         ops.sync()
 
     # ------------------------------------------------------------------ sort / TopK

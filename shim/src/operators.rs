@@ -167,6 +167,11 @@ impl GpuUnaryExec {
                 "count" => sys::DFGPU_AGG_COUNT,
                 "min" => sys::DFGPU_AGG_MIN,
                 "max" => sys::DFGPU_AGG_MAX,
+                // variance.rs / stddev.rs: the registered names and their aliases
+                "var" | "var_samp" | "var_sample" => sys::DFGPU_AGG_VAR_SAMP,
+                "var_pop" | "var_population" => sys::DFGPU_AGG_VAR_POP,
+                "stddev" | "stddev_samp" => sys::DFGPU_AGG_STDDEV_SAMP,
+                "stddev_pop" => sys::DFGPU_AGG_STDDEV_POP,
                 _ => return None,
             };
             if f.is_distinct() || !f.order_bys().is_empty() || f.expressions().len() > 1 {
@@ -183,10 +188,17 @@ impl GpuUnaryExec {
             // AVG over Decimal128(p > 25) sums in Decimal256 (avg_sum_data_type, average.rs:131-172); MIN / MAX over
             // Decimal128(p > 18) compares 128-bit values, the device 64-bit words (aggregate.hip wide_minmax_values_fit)
             if raw {
-                if let Some(DataType::Decimal128(p, _)) = exprs.first().and_then(|e| e.data_type(&in_schema).ok()) {
+                let arg_type = exprs.first().and_then(|e| e.data_type(&in_schema).ok());
+                if let Some(DataType::Decimal128(p, _)) = arg_type {
                     if (func == sys::DFGPU_AGG_AVG && p + 13 > 38) || ((func == sys::DFGPU_AGG_MIN || func == sys::DFGPU_AGG_MAX) && p > 18) {
                         return None;
                     }
+                }
+                // VAR / STDDEV read a Float64, Int32 or Int64 argument (aggregate.hip plan_for); the planner casts to Float64
+                if (sys::DFGPU_AGG_VAR_SAMP..=sys::DFGPU_AGG_STDDEV_POP).contains(&func)
+                    && !matches!(arg_type, Some(DataType::Float64 | DataType::Int32 | DataType::Int64))
+                {
+                    return None;
                 }
             }
             // Final modes cannot derive AVG(Decimal128)'s declared type from its state: AggregateFunctionExpr::return_field carries it
