@@ -845,10 +845,13 @@ struct VarAcc {
   unsigned long long* cnt;          // [G] the node's state
   double* mean;
   double* m2;
+  double* pivot;                    // [G] a group whose batch sum overflowed: one of its values, and the sum of the deviations from it
+  double* bshift;
 };
 struct VarSet {
   VarAcc a[MAX_AGGS];
   int n;
+  uint32_t* overflowed;             // k_var_center found a batch sum beyond DBL_MAX (the passes k_var_pivot .. k_var_recenter run)
 };
 // final modes: the count a partial row brings (0 = skipped: a NULL state column or an empty partial group) and count · mean
 __global__ __launch_bounds__(BLOCK) void k_var_weight(const unsigned long long* __restrict__ n_in, const uint64_t* __restrict__ n_valid, const double* __restrict__ mean_in,
@@ -865,7 +868,54 @@ __global__ __launch_bounds__(BLOCK) void k_var_center(VarSet s, int64_t G) {
   for (int64_t g = (int64_t)blockIdx.x * BLOCK + threadIdx.x; g < G; g += (int64_t)gridDim.x * BLOCK)
     for (int k = 0; k < s.n; k++) {
       const unsigned long long c = s.a[k].bn[g];
-      if (c) s.a[k].bmean[g] = s.a[k].bmean[g] / (double)c;
+      if (!c) continue;
+      const double m = s.a[k].bmean[g] / (double)c;
+      s.a[k].bmean[g] = m;
+      if (!isfinite(m)) *s.overflowed = 1u;
+    }
+}
+// A batch sum beyond DBL_MAX (300 x DBL_MAX) leaves no mean to take deviations from, where variance.rs's running mean stays finite and
+// VAR is 0.0 (tests/test_gpu_edge_values.py::test_variance_over_infinities_nans_and_dbl_max).  Such a group is summed again as deviations
+// from one of its own values (the pivot): mean = pivot + Σ(x - pivot) / n, exact for equal values, non-finite only where the spread is.
+// The three passes return at once when no group overflowed.
+__device__ __forceinline__ bool var_value(const VarAcc& v, int64_t i, double& x, double& w) {
+  if (v.n_in) {
+    const unsigned long long c = v.n_in[i];
+    if (!c) return false;
+    x = ((const double*)v.x)[i];
+    w = (double)c;
+    return true;
+  }
+  if (v.valid && !bit_at(v.valid, i)) return false;
+  switch (v.val) {
+    case VAL_I32_TO_F64: x = (double)((const int32_t*)v.x)[i]; break;
+    case VAL_I64_TO_F64: x = (double)((const int64_t*)v.x)[i]; break;
+    default: x = ((const double*)v.x)[i]; break;
+  }
+  w = 1.0;
+  return true;
+}
+template <bool SHIFT>
+__global__ __launch_bounds__(BLOCK) void k_var_pivot(InternCtx c, const uint32_t* __restrict__ slot_gid, int has_groups, int64_t row_offset, int64_t n, VarSet s) {
+  if (!*s.overflowed) return;
+  for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
+    const uint32_t gid = has_groups ? lookup_gid(c, slot_gid, row_offset + i) : 0u;
+    for (int k = 0; k < s.n; k++) {
+      const VarAcc& v = s.a[k];
+      double x, w;
+      if (isfinite(v.bmean[gid]) || !var_value(v, i, x, w)) continue;
+      if (SHIFT) atomicAdd(&v.bshift[gid], w * (x - v.pivot[gid]));
+      else v.pivot[gid] = x;   // any one value of the group will do
+    }
+  }
+}
+__global__ __launch_bounds__(BLOCK) void k_var_recenter(VarSet s, int64_t G) {
+  if (!*s.overflowed) return;
+  for (int64_t g = (int64_t)blockIdx.x * BLOCK + threadIdx.x; g < G; g += (int64_t)gridDim.x * BLOCK)
+    for (int k = 0; k < s.n; k++) {
+      const VarAcc& v = s.a[k];
+      const unsigned long long c = v.bn[g];
+      if (c && !isfinite(v.bmean[g])) v.bmean[g] = v.pivot[g] + v.bshift[g] / (double)c;
     }
 }
 // what row i adds to its group's m2 (false: nothing, a NULL argument or a skipped partial row)
@@ -934,7 +984,9 @@ __global__ __launch_bounds__(BLOCK) void k_var_merge(VarSet s, int64_t G) {
       }
       const double ma = v.mean[g], fa = (double)na, fb = (double)nb, nt = fa + fb, d = ma - mb;
       v.cnt[g] = na + nb;
-      v.mean[g] = ma * fa / nt + mb * fb / nt;
+      // (ma · na overflows for means near DBL_MAX: then the same mean as ma - d · nb / n; equal means stay exact)
+      const double m = ma * fa / nt + mb * fb / nt;
+      v.mean[g] = d == 0.0 ? ma : isfinite(m) ? m : ma - d * (fb / nt);
       v.m2[g] = v.m2[g] + m2b + d * d * fa * fb / nt;
     }
 }
@@ -4601,6 +4653,9 @@ static void agg_update_unfused(Aggregate& A, const Table& in) {
       v.cnt = a.cnt->as<unsigned long long>();
       v.mean = a.lo->as<double>();
       v.m2 = a.hi->as<double>();
+      for (int b = 0; b < 2; b++) var_bufs.push_back(make_zero_buf((size_t)G1 * 8));
+      v.pivot = var_bufs[var_bufs.size() - 2]->as<double>();
+      v.bshift = var_bufs[var_bufs.size() - 1]->as<double>();
       v.x = inputs[k].v.ptr();
       AccDesc c{}, d{};
       c.acc_lo = v.bn;
@@ -4691,8 +4746,17 @@ static void agg_update_unfused(Aggregate& A, const Table& in) {
   DFGPU_HIP(hipGetLastError());
   if (vars.n > 0) {
     // VAR / STDDEV: the batch's means, the squared deviations from them (a second read of the argument), the merge into the state
+    var_bufs.push_back(make_zero_buf(8));
+    vars.overflowed = var_bufs.back()->as<uint32_t>();
     k_var_center<<<grid_for(G1, BLOCK), BLOCK, 0, r.stream>>>(vars, G1);
     DFGPU_HIP(hipGetLastError());
+    {
+      const int g = std::min(grid_for(n, BLOCK), 1024);
+      k_var_pivot<false><<<g, BLOCK, 0, r.stream>>>(ictx, sg, ngk > 0, G0, n, vars);
+      k_var_pivot<true><<<g, BLOCK, 0, r.stream>>>(ictx, sg, ngk > 0, G0, n, vars);
+      k_var_recenter<<<grid_for(G1, BLOCK), BLOCK, 0, r.stream>>>(vars, G1);
+      DFGPU_HIP(hipGetLastError());
+    }
     {
       ProfileScope ps("agg_var_m2", n * 8 * vars.n * (final_mode ? 3 : 1));
       if (G1 * vars.n <= LDS_CELLS) {

@@ -158,15 +158,14 @@ struct KeySet {
 
 __device__ __forceinline__ bool bit_at(const uint64_t* words, int64_t i) { return (words[i >> 6] >> (i & 63)) & 1ull; }
 
-// value widened to (lo, hi): signed ints sign-extended, floats by bit pattern with
-// -0.0 -> +0.0 (hash_utils.rs:258-276)
+// value widened to (lo, hi): signed ints sign-extended, floats by their bit pattern (hash_utils.rs hash_float_value hashes
+// f64::to_ne_bytes: -0.0 and +0.0 hash apart and route to their own partitions, tests/test_gpu_edge_values.py::test_partition)
 __device__ __forceinline__ void load_words(const KeyCol& k, int64_t i, uint64_t& lo, uint64_t& hi) {
   hi = 0;
   switch (k.type) {
     case 1: case 8: lo = (uint64_t)(int64_t)((const int32_t*)k.data)[i]; break;  // INT32 / DATE32
     case 6: lo = ((const uint32_t*)k.data)[i]; break;
-    case 2: case 7: lo = ((const uint64_t*)k.data)[i]; break;
-    case 4: { uint64_t b = ((const uint64_t*)k.data)[i]; lo = (b << 1) == 0 ? 0 : b; break; }
+    case 2: case 4: case 7: lo = ((const uint64_t*)k.data)[i]; break;
     case 5: lo = ((const uint8_t*)k.data)[i]; break;
     case 3: { const uint64_t* p = (const uint64_t*)k.data + 2 * i; lo = p[0]; hi = p[1]; break; }
     default: lo = 0;
@@ -213,10 +212,10 @@ __device__ __forceinline__ uint64_t hash_row(const KeySet& ks, int64_t i, uint64
   }
   return h;
 }
-// equal_rows_arr (joins/utils.rs:2191-2260).  `float_total_order`: the join compares Float64 keys with arrow-ord's eq — IEEE 754
-// totalOrder equality, i.e. equality of the bit patterns: -0.0 and +0.0 are different keys (they still hash alike) —
-// which is what the oracle restates (dforacle.c keys_equal)
-__device__ __forceinline__ bool keys_equal(const KeySet& a, int64_t ia, const KeySet& b, int64_t ib, bool null_equals_null, bool float_total_order = false) {
+// equal_rows_arr (joins/utils.rs:2191-2260).  Float64 keys compare as arrow-ord's eq does — IEEE 754 totalOrder equality, i.e.
+// equality of the bit patterns that load_words gives: -0.0 and +0.0 are different join keys and different GROUP BY groups, which is
+// what the oracle restates (dforacle.c keys_equal)
+__device__ __forceinline__ bool keys_equal(const KeySet& a, int64_t ia, const KeySet& b, int64_t ib, bool null_equals_null) {
   for (int c = 0; c < a.n; c++) {
     bool va = !a.c[c].valid || bit_at(a.c[c].valid, ia);
     bool vb = !b.c[c].valid || bit_at(b.c[c].valid, ib);
@@ -227,10 +226,6 @@ __device__ __forceinline__ bool keys_equal(const KeySet& a, int64_t ia, const Ke
     uint64_t alo, ahi, blo, bhi;
     load_words(a.c[c], ia, alo, ahi);
     load_words(b.c[c], ib, blo, bhi);
-    if (float_total_order && a.c[c].type == 4) {
-      alo = ((const uint64_t*)a.c[c].data)[ia];
-      blo = ((const uint64_t*)b.c[c].data)[ib];
-    }
     if (alo != blo || ahi != bhi) return false;
   }
   return true;

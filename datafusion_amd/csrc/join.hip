@@ -489,7 +489,7 @@ __global__ __launch_bounds__(BLOCK) void k_hm_check_unique(KeySet ks, int64_t n,
   for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
     uint32_t cur = next[i];
     while (cur) {
-      if (keys_equal(ks, i, ks, (int64_t)cur - 1, null_equals_null, true)) { *dup_flag = 1; break; }
+      if (keys_equal(ks, i, ks, (int64_t)cur - 1, null_equals_null)) { *dup_flag = 1; break; }
       cur = next[cur - 1];
     }
   }
@@ -661,7 +661,7 @@ __device__ __forceinline__ uint32_t chain_head(const ProbeCtx& c, int64_t p) {
 template <int KIND>
 __device__ __forceinline__ bool chain_match(const ProbeCtx& c, int64_t b, int64_t p) {
   if (KIND != KIND_HASH) return true;  // direct addressing / inline keys: same slot <=> same key
-  return keys_equal(c.bkeys, b, c.pkeys, p, c.null_equals_null, true);
+  return keys_equal(c.bkeys, b, c.pkeys, p, c.null_equals_null);
 }
 
 // match ids (build row + 1, 0 = none) of N consecutive 64-row probe words for this lane.  Every

@@ -600,7 +600,7 @@ __global__ __launch_bounds__(BLOCK) void k_rj_join(const uint64_t* __restrict__ 
         if (!EMIT) {
           while (cur) {
             const uint32_t bi = cur - 1;
-            if (s_key[bi] == k && (EXACT || keys_equal(v.bkeys, (int64_t)brid[c0 + bi], v.pkeys, (int64_t)pr, v.null_equals_null != 0, true))) mine++;
+            if (s_key[bi] == k && (EXACT || keys_equal(v.bkeys, (int64_t)brid[c0 + bi], v.pkeys, (int64_t)pr, v.null_equals_null != 0))) mine++;
             cur = s_next[bi];
           }
           continue;
@@ -627,7 +627,7 @@ __global__ __launch_bounds__(BLOCK) void k_rj_join(const uint64_t* __restrict__ 
           uint32_t bi = 0;
           if (cur) {
             bi = cur - 1;
-            hit = s_key[bi] == k && (EXACT || keys_equal(v.bkeys, (int64_t)brid[c0 + bi], v.pkeys, (int64_t)pr, v.null_equals_null != 0, true));
+            hit = s_key[bi] == k && (EXACT || keys_equal(v.bkeys, (int64_t)brid[c0 + bi], v.pkeys, (int64_t)pr, v.null_equals_null != 0));
             cur = s_next[bi];
           }
           const uint64_t hm = ballot64(hit);

@@ -846,6 +846,9 @@ def unsupported_reason(node):
                 if func in ("min", "max") and pa.types.is_decimal128(t) and t.precision > 18:
                     # aggregate.hip wide_minmax_values_fit: the device compares 64-bit words; values beyond them are only found at run time
                     return f"{func.upper()}({n}) over {t}: values of more than 18 digits do not fit the device's 64-bit comparison"
+                if func in ("min", "max") and t == pa.uint64():
+                    # aggregate.hip plan_for: MIN / MAX use signed 64-bit atomics (tests/test_gpu_edge_values.py::test_min_max_over_uint64_is_refused_and_stays_on_the_cpu)
+                    return f"{func.upper()}({n}) over UInt64 is not supported on the GPU path"
                 if func in ("sum", "avg", "min", "max") and (pa.types.is_boolean(t) or pa.types.is_string(t) or pa.types.is_large_string(t)):
                     return f"{func.upper()}({n}) over {t} is not supported on the GPU path"
                 if func in ops.VARIANCE_FUNCS and t not in (pa.float64(), pa.int32(), pa.int64()):

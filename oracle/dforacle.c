@@ -41,15 +41,15 @@ static inline uint64_t fmix64(uint64_t x) {
 }
 static inline uint64_t hash_u64(uint64_t v, uint64_t seed) { return fmix64(v ^ seed ^ 0x9E3779B97F4A7C15ULL); }
 
-/* value of row i widened to (lo, hi); hash_utils.rs:258-276: floats hash by bit
- * pattern with -0.0 normalised to +0.0 */
+/* value of row i widened to (lo, hi); hash_utils.rs hash_float_value: floats hash by
+ * their bit pattern (f64::to_ne_bytes), so -0.0 and +0.0 route apart
+ * (tests/test_edge_values_oracle.py::test_hash_routing_follows_the_float_bits) */
 static inline void load_words(const orc_col* c, int64_t i, uint64_t* lo, uint64_t* hi) {
   *hi = 0;
   switch (c->type) {
     case ORC_I32: *lo = (uint64_t)(int64_t)((const int32_t*)c->data)[i]; break;
     case ORC_U32: *lo = ((const uint32_t*)c->data)[i]; break;
-    case ORC_I64: case ORC_U64: *lo = ((const uint64_t*)c->data)[i]; break;
-    case ORC_F64: { uint64_t b = ((const uint64_t*)c->data)[i]; *lo = (b << 1) == 0 ? 0 : b; break; }
+    case ORC_I64: case ORC_U64: case ORC_F64: *lo = ((const uint64_t*)c->data)[i]; break;
     case ORC_U8: *lo = ((const uint8_t*)c->data)[i]; break;
     case ORC_I128: *lo = ((const uint64_t*)c->data)[2 * i]; *hi = ((const uint64_t*)c->data)[2 * i + 1]; break;
     default: *lo = 0;
@@ -666,16 +666,23 @@ int orc_accumulate(int op, const orc_col* values, const int64_t* gids, int64_t n
       const i128 mn = (i128)((u128)1 << 127), mx = ~mn;
       ACC_LOOP(i128, u128, mn, mx); return 0;
     }
+    case ORC_U32: ACC_LOOP(uint32_t, uint32_t, 0, UINT32_MAX); return 0;
+    case ORC_U64: ACC_LOOP(uint64_t, uint64_t, 0, UINT64_MAX); return 0;
     case ORC_F64: {
+      /* MIN / MAX compare by f64::total_cmp, as arrow-arith's min / max kernels order floats (aggregate.rs, `max`: NaN is greater
+       * than every other value, -0.0 is less than +0.0): the first value of a group is taken as it is, so MAX over a NaN is that NaN
+       * and MIN(-0.0, +0.0) is -0.0 (tests/test_edge_values_oracle.py::test_min_max_follow_the_total_order) */
       const double* v = (const double*)values->data; double* o = (double*)out;
-      for (int64_t g = 0; g < ngroups; g++) o[g] = op == 0 ? 0.0 : op == 1 ? INFINITY : -INFINITY;
+      for (int64_t g = 0; g < ngroups; g++) o[g] = 0.0;
       for (int64_t i = 0; i < n; i++) {
         if (sel && !sel[i]) continue;
         if (!col_valid(values, i)) continue;
-        int64_t g = gids[i]; out_seen[g] = 1;
+        int64_t g = gids[i];
         if (op == 0) o[g] += v[i];
-        else if (op == 1) { if (v[i] < o[g]) o[g] = v[i]; }
-        else { if (v[i] > o[g]) o[g] = v[i]; }
+        else if (!out_seen[g]) o[g] = v[i];
+        else if (op == 1) { if (f64_total_key(v[i]) < f64_total_key(o[g])) o[g] = v[i]; }
+        else { if (f64_total_key(v[i]) > f64_total_key(o[g])) o[g] = v[i]; }
+        out_seen[g] = 1;
       }
       return 0;
     }

@@ -640,6 +640,8 @@ def sum_result_type(t: pa.DataType) -> pa.DataType:
         return pa.decimal128(min(38, t.precision + 10), t.scale)
     if pa.types.is_int32(t) or pa.types.is_int64(t):
         return pa.int64()
+    if pa.types.is_uint32(t):
+        return pa.uint64()        # SUM over unsigned integers is UInt64 (sum.rs coerce_types)
     return t
 
 
@@ -724,6 +726,8 @@ def aggregate(table: pa.Table, group_by, aggs, mode="Single", return_types=None)
             varr = evaluate(e, table).to_array(n)
         if not final and func in ("sum", "avg") and (pa.types.is_int32(varr.type) or pa.types.is_uint8(varr.type)):
             varr = varr.cast(pa.int64())
+        if not final and func == "sum" and pa.types.is_uint32(varr.type):
+            varr = varr.cast(pa.uint64())
         if not final and func == "avg" and pa.types.is_int64(varr.type):
             varr = varr.cast(pa.float64())  # AVG over integers is coerced to Float64 (average.rs coerce_types)
         t = orc_type(varr.type)

@@ -138,7 +138,7 @@ def test_flat_table_packed_keys(keys, join_type):
     rcols = {f"j{i}": t for i, t in enumerate(spec)}
     left = random_table(rng, 2500, {**lcols, "v": (pa.int64(), 0, 10**9)}, null_frac=0.04)
     right = random_table(rng, 6000, {**rcols, "w": (pa.decimal128(15, 2), 0, 10**6)}, null_frac=0.04)
-    if keys == "date_u8ish_f64":   # few distinct doubles, -0.0 among them (hash_utils.rs:258-276: -0.0 and +0.0 are one key)
+    if keys == "date_u8ish_f64":   # few distinct doubles, -0.0 among them (-0.0 and +0.0 are two keys: equal by their bits)
         vals = np.array([0.0, -0.0, 1.5, -2.25, 1e300])
         for t, name, n in ((left, "k1", 2500), (right, "j1", 6000)):
             arr = pa.array(vals[rng.integers(0, 5, n)], mask=rng.random(n) < 0.04)
