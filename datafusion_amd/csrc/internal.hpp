@@ -178,6 +178,9 @@ struct DevBuf {
   // question (what was asked, of which rows), bits 1..0 = 2 | answer.  The join's "are these probe keys clustered?" sample lives here:
   // asked once per table instead of once per probe (a kernel and a blocking read-back each time).
   std::atomic<uint64_t> hint{0};
+  // A second remembered answer, same layout: "does every row of this (probe key) buffer find its key in THAT build side?" — the
+  // all-hit sample of join_probe, tagged with the build side's key buffers and shape.  Only ever a hint: the probe kernel verifies.
+  std::atomic<uint64_t> all_hit_hint{0};
   explicit DevBuf(size_t n);
   DevBuf(void* p, size_t n, std::shared_ptr<void> keep_alive) : ptr(p), bytes(n), foreign(std::move(keep_alive)) {}
   ~DevBuf();

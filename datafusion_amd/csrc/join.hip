@@ -1390,6 +1390,83 @@ __global__ __launch_bounds__(BLOCK, ((KIND == KIND_FLAT || KIND == KIND_FLAT16) 
   }
 }
 
+// ---------------------------------------------------------------- the foreign-key probe that shares its probe columns
+// Every probe row finds exactly one build row and the output is in probe order: output row i IS probe row i, so the output's
+// probe-side columns are the probe table's own (immutable, reference-counted) columns and only the build-side columns are new.
+// This kernel reads the keys, looks them up, gathers the build payload and writes it at output row = probe row: no tile offsets, so
+// no LDS, no barrier, no cursor — waves are independent.  A row without a partner raises FusedCtl::ticket (the host then starts
+// over with the counting flavours); rows that did hit still write their own slot only, never outside the np-row allocation.
+// cols.n_build == 0 (a RightSemi probe whose every row hits): keys read and verified, nothing written.
+// Measured on the SF100 headline (600 M rows, two 4-byte build columns; profiles/join_shared_probe.md): W = 1 / 2 / 4 / 8 words per
+// wave 3.75 / 2.76 / 2.48 / 2.31 ms; a 4-byte column leaving as one 16-byte store per lane (below) instead of four 4-byte ones
+// 2.31 -> 1.82-1.93 ms: narrow stores are bound by their number, not their bytes; plain against non-temporal stores: no difference.
+constexpr int SHARED_W = 8;  // 64-row words per wave
+template <int KIND, int KT, int W>
+__global__ __launch_bounds__(BLOCK) void k_join_probe_shared(ProbeCtx c, JoinCopyCols cols, int64_t np, FusedCtl* __restrict__ ctl) {
+  static_assert(W % 4 == 0, "4-byte columns leave four words (256 rows) at a time");
+  const int64_t n_words = (np + 63) >> 6;
+  const unsigned lane = lane_id();
+  const int64_t w0 = ((((int64_t)blockIdx.x * BLOCK) + threadIdx.x) >> 6) * W;
+  if (w0 >= n_words) return;   // (wave-uniform)
+  uint32_t m[W];
+  lookup_words<KIND, KT, W>(c, w0, np, m);
+  bool missed = false;
+#pragma unroll
+  for (int j = 0; j < W; j++) missed |= (((w0 + j) << 6) + lane) < np && m[j] == 0;
+  const uint64_t miss_word = ballot64(missed);
+  if (miss_word && lane == (unsigned)__builtin_ctzll(miss_word)) ctl->ticket = 1u;   // a plain store from one lane: every writer writes the same value
+  for (int cidx = 0; cidx < cols.n_build; cidx++) {
+    const int width = cols.width[cidx];
+    if (width == 4) {
+      // the lookup leaves lane L with row L of each word; the stores want lane L to hold rows 4 L .. 4 L + 3 of a 256-row group
+      // (all four in word L / 16): a 4 x 4 exchange through the wave's lanes, then ONE 16-byte store per lane
+#pragma unroll
+      for (int g = 0; g < W / 4; g++) {
+        uint32_t v[4], o[4];
+#pragma unroll
+        for (int jj = 0; jj < 4; jj++) {
+          const int j = 4 * g + jj;
+          const bool live = (((w0 + j) << 6) + lane) < np && m[j];
+          v[jj] = live ? reinterpret_cast<const uint32_t*>(cols.src[cidx])[m[j] - 1] : 0u;   // (a row that missed: the run is void, its slot gets 0)
+        }
+        const int word_of_lane = lane >> 4;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          const int from = (4 * lane + q) & 63;
+#pragma unroll
+          for (int jj = 0; jj < 4; jj++) {
+            const uint32_t t = __shfl(v[jj], from);
+            if (jj == word_of_lane) o[q] = t;
+          }
+        }
+        const int64_t row0 = ((w0 + 4 * g) << 6) + 4 * (int64_t)lane;
+        uint32_t* dst = reinterpret_cast<uint32_t*>(cols.dst[cidx]) + row0;   // (row0 % 4 == 0 and a fresh column starts where its buffer starts: 16-byte aligned)
+        if (row0 + 3 < np) {
+          stream_store(reinterpret_cast<uint4*>(dst), make_uint4(o[0], o[1], o[2], o[3]));
+        } else {
+#pragma unroll
+          for (int q = 0; q < 4; q++)
+            if (row0 + q < np) dst[q] = o[q];
+        }
+      }
+      continue;
+    }
+#pragma unroll
+    for (int j = 0; j < W; j++) {
+      const int64_t d = ((w0 + j) << 6) + lane;
+      if (d >= np || !m[j]) continue;
+      const int64_t s = (int64_t)m[j] - 1;
+      // build rows are re-read by neighbouring probe rows (plain loads); the output is written once and not read here (jcopy_stream's
+      // `full` form)
+      switch (width) {
+        case 16: jcopy_stream<uint4>(cols.src[cidx], cols.dst[cidx], s, d, false, true); break;
+        case 8: jcopy_stream<uint64_t>(cols.src[cidx], cols.dst[cidx], s, d, false, true); break;
+        case 1: jcopy_stream<uint8_t>(cols.src[cidx], cols.dst[cidx], s, d, false, true); break;
+      }
+    }
+  }
+}
+
 // ---------------------------------------------------------------- the selective probe (direct-address kinds)
 // A probe that emits few of its rows is made of latency, not of bytes: in the fused kernel every tile walks key -> table ->
 // (rank -> row) -> barrier -> offset -> a load/store round trip per column with a few lanes alive, at the 5 waves per SIMD
@@ -2534,6 +2611,20 @@ static bool probe_keys_clustered(const Column& kc, int64_t n, uint64_t window) {
   return clustered;
 }
 
+// The tag under which the all-hit question of one (build side, probe key columns) pair is remembered in the first probe key
+// buffer's DevBuf::all_hit_hint: the key buffers of both sides (tables are immutable, so the same buffers and shapes give the same
+// answer; a recycled address can only make the hint wrong, and the probe kernel verifies what the hint promises), bits 1..0 free.
+static uint64_t all_hit_tag(const JoinTable& jt, const Table& probe, const std::vector<int>& pk, int kind) {
+  uint64_t h = fmix64((uint64_t)probe.nrows * 0x9E3779B97F4A7C15ull ^ (uint64_t)jt.build.nrows ^ ((uint64_t)kind << 56));
+  for (size_t i = 0; i < pk.size(); i++) {
+    const Column& p = probe.cols[(size_t)pk[i]];
+    const Column& b = jt.build.cols[(size_t)jt.key_cols[i]];
+    h = fmix64(h ^ (uint64_t)(uintptr_t)p.ptr()) ^ fmix64((uint64_t)(uintptr_t)p.valid_words() + i);
+    h = fmix64(h ^ (uint64_t)(uintptr_t)b.ptr()) ^ fmix64((uint64_t)(uintptr_t)b.valid_words() + 2 * i + 1);
+  }
+  return (h & ~3ull) | 2ull;
+}
+
 // do 64 K evenly spaced probe rows ALL find their key?  (the speculation of the placed probe is only worth trying then)
 template <int KIND, int KT>
 __global__ __launch_bounds__(BLOCK) void k_sample_all_hit(ProbeCtx c, int64_t np, int64_t every_words, int samples, int* __restrict__ misses) {
@@ -2973,25 +3064,123 @@ static Table join_probe(JoinTable& jt, const Table& probe, const std::vector<int
     BufPtr out_words;
     int64_t n_alloc = np;
     // ---- speculation for the probe-order output: a foreign-key probe (every row finds its key) needs no counts pass — row i of
-    // the output IS probe row i.  64 K sampled rows that all hit make it worth trying; the kernel verifies every tile and the
+    // the output IS probe row i.  64 K sampled rows that all hit make it worth trying; the kernel verifies every row and the
     // host starts over with the counts when one disagrees (the reference's order, exec.rs:3349, at the unordered flavour's cost)
     static thread_local bool no_speculation = false;
+    DevBuf* hit_hint = nullptr;   // where the sample's answer is remembered (all_hit_tag), when it was asked
+    uint64_t hit_tag = 0;
+    // the same probe again, counted: what a speculation that met a row without a partner falls back to
+    auto probe_again_counted = [&](hipEvent_t ea, hipEvent_t eb) {
+      if (hit_hint) hit_hint->all_hit_hint.store(hit_tag, std::memory_order_relaxed);   // (the sample was wrong about these rows: not asked again)
+      if (r.profiling) {
+        std::lock_guard<std::mutex> lk(r.mu);
+        r.recs.push_back(Runtime::Rec{"join_probe_speculation_missed", ea, eb, 0, std::this_thread::get_id()});
+      }
+      {
+        std::lock_guard<std::mutex> lk(jt.mu);
+        jt.info.probe_rows -= np;
+      }
+      out = Table{};   // (the half-made output goes back to the pool first)
+      no_speculation = true;
+      Table again;
+      try {
+        again = join_probe(jt, probe, pk, join_type, bout_in, pout, row_mask, mask_consumed);
+      } catch (...) {
+        no_speculation = false;
+        throw;
+      }
+      no_speculation = false;
+      return again;
+    };
     bool speculate = false;
+    const bool spec_kind = kind == KIND_RANK || kind == KIND_ARRAY || kind == KIND_FLAT || kind == KIND_FLAT16;
+    // from how many probe rows the sample (a kernel and a blocking read-back) is worth its answer
+    const bool may_sample = !row_mask && !lazy && !invert && !no_speculation && spec_kind && np >= option_int("join.share_probe_min_rows", 1 << 22);
+    // ---- the shared flavour (k_join_probe_shared): when every row hits and the output is in probe order — required by probe_mode
+    // 0 / 1, one admissible order for 3 / 4 — the output's probe-side columns ARE the probe table's columns (immutable, reference-
+    // counted buffers: second owners, as dfgpu_table_select hands out) and only the build-side columns are written.  `listed` resting
+    // on the key-density guess alone does not keep an all-hit probe away: the sample is asked first, and a sample that finds a miss
+    // leaves `listed` and everything below as it was.
+    const bool share_wanted = option_on("join.share_probe", true) && jt.probe_mode != 2 && !returned && (fast_inner || join_type == DFGPU_JOIN_RIGHT_SEMI);
     if (returned_all_hit && !no_speculation) {
       speculate = true;   // (not a guess here: the grouped lookup counted its hits; the kernel's per-tile check stays as the safety net)
-    } else if (fused_mode == FUSED_PLACED && !listed && !row_mask && !invert && !no_speculation && np >= (1 << 22) &&
-               (kind == KIND_RANK || kind == KIND_ARRAY || kind == KIND_FLAT || kind == KIND_FLAT16) &&
-        true) {
-      constexpr int S = 1024;  // sampled words
-      BufPtr miss = make_zero_buf(4);
+    } else if (may_sample && (share_wanted || (fused_mode == FUSED_PLACED && !listed))) {
+      // asked before of these key buffers?  (a kernel and a blocking read-back, 0.04 ms, on every unmasked fused probe otherwise)
+      hit_hint = probe.cols[(size_t)pk[0]].data.get();
+      hit_tag = all_hit_tag(jt, probe, pk, kind);
+      const uint64_t h = hit_hint->all_hit_hint.load(std::memory_order_relaxed);
+      if ((h & ~1ull) == hit_tag) {
+        speculate = (h & 1ull) != 0;
+      } else {
+        constexpr int S = 1024;  // sampled words
+        BufPtr miss = make_zero_buf(4);
+        with_kind_and_key(kind, ctx.pkeys.c[0].type, [&](auto kd, auto kt) {
+          k_sample_all_hit<decltype(kd)::value, decltype(kt)::value><<<S * WAVE / BLOCK, BLOCK, 0, r.stream>>>(ctx, np, std::max<int64_t>(1, n_words / S), S, miss->as<int>());
+        });
+        DFGPU_HIP(hipGetLastError());
+        int m = 0;
+        d2h(&m, miss->ptr, 4);
+        speculate = m == 0;
+        hit_hint->all_hit_hint.store(hit_tag | (speculate ? 1ull : 0ull), std::memory_order_relaxed);
+      }
+    }
+    if (speculate && share_wanted && !returned_all_hit) {
+      need_tab();   // (a probe `listed` by the guess has not asked for the interleaved rank table yet)
+      JoinCopyCols jc{};
+      jc.key_col = -1;
+      int64_t bytes = key_bytes;   // what this launch moves: the keys once, the build payload once, the build-side output once
+      for (int c : bout) {
+        const Column& sc = jt.build.cols[c];
+        out.cols.push_back(alloc_like(sc, np));
+        jc.src[jc.n] = sc.ptr();
+        jc.dst[jc.n] = out.cols.back().data->ptr;
+        jc.width[jc.n] = type_width(sc.field.type);
+        bytes += (jt.build.nrows + np) * jc.width[jc.n];
+        jc.n++;
+      }
+      jc.n_build = jc.n;
+      hipEvent_t ea = nullptr, eb = nullptr, sa = nullptr, sb = nullptr;
+      if (r.profiling) {
+        for (hipEvent_t* e : {&ea, &eb, &sa, &sb}) DFGPU_HIP(hipEventCreate(e));
+        DFGPU_HIP(hipEventRecord(ea, r.stream));
+      }
       with_kind_and_key(kind, ctx.pkeys.c[0].type, [&](auto kd, auto kt) {
-        k_sample_all_hit<decltype(kd)::value, decltype(kt)::value><<<S * WAVE / BLOCK, BLOCK, 0, r.stream>>>(ctx, np, std::max<int64_t>(1, n_words / S), S, miss->as<int>());
+        constexpr int K = decltype(kd)::value, T = decltype(kt)::value;
+        if constexpr (K == KIND_RANK || K == KIND_ARRAY || K == KIND_FLAT || K == KIND_FLAT16) {
+          const int64_t waves = (n_words + SHARED_W - 1) / SHARED_W;
+          const unsigned g = (unsigned)((waves + BLOCK / WAVE - 1) / (BLOCK / WAVE));
+          k_join_probe_shared<K, T, SHARED_W><<<g, BLOCK, 0, r.stream>>>(ctx, jc, np, ctl->as<FusedCtl>());
+        }
       });
       DFGPU_HIP(hipGetLastError());
-      int m = 0;
-      d2h(&m, miss->ptr, 4);
-      speculate = m == 0;
+      if (r.profiling) {
+        DFGPU_HIP(hipEventRecord(eb, r.stream));
+        DFGPU_HIP(hipEventRecord(sa, r.stream));
+        DFGPU_HIP(hipEventRecord(sb, r.stream));
+      }
+      unsigned missed = 0;   // the one read-back: the output's row count is np without asking
+      d2h(&missed, &ctl->as<FusedCtl>()->ticket, 4);
+      if (missed) {
+        if (r.profiling) {
+          DFGPU_HIP(hipEventDestroy(sa));
+          DFGPU_HIP(hipEventDestroy(sb));
+        }
+        return probe_again_counted(ea, eb);
+      }
+      for (int c : pout) {   // second owners of the probe's buffers; the rows are the same rows, so the statistics stay
+        out.cols.push_back(probe.cols[c]);
+        out.cols.back().length = np;
+      }
+      if (r.profiling) {
+        std::lock_guard<std::mutex> lk(r.mu);
+        r.recs.push_back(Runtime::Rec{want_single ? "join_probe_fused" : "join_probe_placed", ea, eb, bytes, std::this_thread::get_id()});
+        r.recs.push_back(Runtime::Rec{"join_probe_shared_columns", sa, sb, 0, std::this_thread::get_id()});   // (which path ran; moves nothing)
+      }
+      out.nrows = np;
+      jt.info.output_rows += out.nrows;
+      return out;
     }
+    speculate = speculate && fused_mode == FUSED_PLACED && !listed;   // (asked for the shared flavour only: nothing else to speculate on)
     if (fused_mode == FUSED_PLACED && !speculate) {
       // pass 1: output rows per tile (reads the probe keys only), then the tiles' exclusive prefix
       BufPtr counts = make_buf((size_t)n_tiles * 4);
@@ -3105,27 +3294,7 @@ static Table join_probe(JoinTable& jt, const Table& probe, const std::vector<int
       if (speculate) {
         unsigned missed = 0;
         d2h(&missed, &ctl->as<FusedCtl>()->ticket, 4);
-        if (missed) {  // some probe row has no partner after all: the same probe again, counted
-          if (r.profiling) {
-            std::lock_guard<std::mutex> lk(r.mu);
-            r.recs.push_back(Runtime::Rec{"join_probe_speculation_missed", ea, eb, 0, std::this_thread::get_id()});
-          }
-          {
-            std::lock_guard<std::mutex> lk(jt.mu);
-            jt.info.probe_rows -= np;
-          }
-          out = Table{};
-          no_speculation = true;
-          Table again;
-          try {
-            again = join_probe(jt, probe, pk, join_type, bout_in, pout, row_mask, mask_consumed);
-          } catch (...) {
-            no_speculation = false;
-            throw;
-          }
-          no_speculation = false;
-          return again;
-        }
+        if (missed) return probe_again_counted(ea, eb);   // some probe row has no partner after all
       }
     } else if (r.profiling) {
       DFGPU_HIP(hipEventRecord(eb, r.stream));

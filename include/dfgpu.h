@@ -477,7 +477,12 @@ int dfgpu_join_estimate_bytes(int64_t build_rows, int64_t build_row_bytes, int64
  * Semi / Anti joins emit one side only; Mark joins append a Boolean `mark` column.
  * For Left/Full/LeftSemi/LeftAnti/LeftMark the probe call emits only what is known per
  * probe batch (matched pairs) and records visited build rows; call
- * dfgpu_join_emit_unmatched once all probe tables are done (stream.rs:1002-). */
+ * dfgpu_join_emit_unmatched once all probe tables are done (stream.rs:1002-).
+ * Output columns may SHARE their device buffers with the probe table (zero-copy, as dfgpu_table_select does): when every
+ * probe row matches exactly one build row and the output is in probe order (a foreign-key probe: Inner over unique build
+ * keys, RightSemi), the probe-side output columns are second owners of the probe table's columns and only the build-side
+ * columns are written.  Tables are immutable and their buffers reference-counted, so either table may be freed first.
+ * Options (dfgpu_set_option): join.share_probe, join.share_probe_min_rows. */
 int dfgpu_join_probe(dfgpu_join_t ht, dfgpu_table_t probe, const int* probe_key_cols, int join_type,
                      const int* build_out_cols, int n_build_out, const int* probe_out_cols, int n_probe_out,
                      dfgpu_table_t* out);
@@ -616,6 +621,8 @@ int dfgpu_agg_fused_updates(dfgpu_agg_t h, int64_t* out);
  *   agg.partitioned = 0|1 (1), agg.partitioned_min_rows (2 x rows worth a pass), agg.grouped_move, agg.direct_table, agg.runs = 0|1 (1)
  *   join.grouped_probe = 0|1 (1), join.grouped_min_rows (rows worth a pass), join.beyond_cache_bytes (4 x the L2 of an XCD),
  *   join.grouped_bits, join.near_window (test hooks: 0 = derived)
+ *   join.share_probe = 0|1 (1: an all-hit probe in probe order hands back the probe table's own columns, dfgpu_join_probe),
+ *   join.share_probe_min_rows (4 Mi: probe rows from which the all-hit sample — a kernel and a read-back — is asked)
  *   join.radix_onesweep = 0|1 (1: the LDS radix join partitions by two or three 8-bit passes straight off the key column; 0: round 5's
  *   record kernel + 6-bit passes), join.radix_tile_threads = 256|512 (512) and join.radix_tile_items = 8|16 (with 256 threads; 16): the partitioning tile, 512 x 8 = 4096 rows by default, join.radix_fused_emit = 0|1 (1),
  *   join.radix_partition_rows (2400: build rows per LDS partition on average; test hook: small values give several passes on small inputs)

@@ -70,7 +70,9 @@ def rocprof_avg_ms(db, line):
         def mode(n):
             a = [x.strip().replace("(dfgpu::FusedMode)", "") for x in n[n.index("<") + 1:].rstrip(">").split(",")] if "<" in n else []
             return a[3] if len(a) >= 4 else ""
-        cand = [r for r in cand if mode(r[0]) == want]
+        # ... or k_join_probe_shared (the foreign-key probe that shares its probe columns), recorded under either scope: whichever
+        # of the two took the time is the kernel behind the scope
+        cand = [r for r in cand if mode(r[0]) == want] + [r for r in rows if r[0].startswith("k_join_probe_shared")]
     if not cand:
         return None, None
     best = max(cand, key=lambda r: r[2])

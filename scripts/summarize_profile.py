@@ -177,11 +177,16 @@ def main():
         if not r["traffic_bytes"] or not bench:
             continue
         if is_join:
-            if not r["kernel"].startswith("k_join_probe_fused"):
+            if r["kernel"].startswith("k_join_probe_shared"):
+                # the foreign-key probe that shares its probe columns: one kernel behind either scope; the bench line says which was asked for
+                name = (bench.get("roofline") or {}).get("kernel")
+                name = name if name in ("join_probe_fused", "join_probe_placed") else None
+            elif r["kernel"].startswith("k_join_probe_fused"):
+                targs = [a.strip() for a in r["kernel"][r["kernel"].index("<") + 1:].rstrip(">").split(",")]   # <KIND, KT, W, MODE, KEYREG>
+                mode = targs[3] if len(targs) >= 4 else ""
+                name = {"0": "join_probe_fused", "2": "join_probe_placed"}.get(mode.replace("(dfgpu::FusedMode)", ""))
+            else:
                 continue
-            targs = [a.strip() for a in r["kernel"][r["kernel"].index("<") + 1:].rstrip(">").split(",")]   # <KIND, KT, W, MODE, KEYREG>
-            mode = targs[3] if len(targs) >= 4 else ""
-            name = {"0": "join_probe_fused", "2": "join_probe_placed"}.get(mode.replace("(dfgpu::FusedMode)", ""))
             if name is None:
                 continue
             wl = {k: bench["config"][k] for k in ("build_rows", "probe_rows", "output_rows", "join_table")}
