@@ -340,7 +340,6 @@ inline dfgpu_table_t wrap_quiet(Table* t) { return reinterpret_cast<dfgpu_table_
 void scan_mask_popcounts(const uint64_t* mask, const uint64_t* valid, int64_t nrows, uint64_t* out_prefix);
 // exclusive prefix sum of u32 counts -> u64 (n + 1 entries)
 void scan_u32(const uint32_t* in, int64_t n, uint64_t* out_prefix);
-void scan_bitmap_words_tab(const uint64_t* words, int64_t n_words, uint64_t* out_prefix, void* out_tab);   // + the rank map's interleaved {word, prefix} pairs
 uint64_t read_u64(const uint64_t* dev);
 
 // ----------------------------------------------------------------- compaction (filter.hip)

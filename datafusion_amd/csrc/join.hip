@@ -77,7 +77,12 @@ struct JoinTable {
   BufPtr rank_bits, rank_prefix, rank_perm;  // rank map: u64 bitmap, u64 exclusive popcount prefix per word, optional u32 perm
   BufPtr rank_tab;  // the probe's view of the rank map: {bitmap word, prefix} interleaved, ONE 16-byte load per lookup; made by the
                     // first probe that looks ranks up row by row (ensure_rank_tab): membership passes and the listed emit read
-                    // rank_bits / rank_prefix
+                    // rank_bits / rank_prefix.
+                    // Ascending keys at a density >= 0.15 have ONLY the table after the build (k_rank_tab_onepass); rank_bits is then
+                    // made from it by the first membership pass (ensure_rank_bits) and rank_prefix never: a rank map always has the
+                    // table or bitmap + prefix, and kernels read either through rank_word / rank_entry.
+                    // CONTRACT: .y (and rank_prefix[w]) is only meaningful under a set bit of .x — a word without a key may hold
+                    // {0, 0}.  Every reader tests the key's bit before it uses the rank; nobody reads the total past the last word.
   std::mutex tab_mu;
   // build keys not in ascending row order: rank != row id, a probe that needs BUILD ROWS (payload columns, visited marks, pairs)
   // goes through the rank -> row permutation — built on the first such probe (ensure_rank_perm), because a probe that only asks
@@ -120,6 +125,20 @@ struct ProbeCtx {
   const uint8_t* ret_rec;
   int ret_R;
 };
+
+// The rank map's bitmap word / {word, prefix} entry from whichever form the table has (uniform over the launch): the bitmap alone is
+// half the bytes per line for a membership pass, the interleaved entry one line instead of two for a rank
+__device__ __forceinline__ uint64_t rank_word(const ProbeCtx& c, uint64_t w) { return c.rank_bits ? c.rank_bits[w] : c.rank_tab[w].x; }
+__device__ __forceinline__ void rank_entry(const ProbeCtx& c, uint64_t w, uint64_t& bits, uint64_t& prefix) {
+  if (c.rank_tab) {
+    const ulonglong2 e = c.rank_tab[w];
+    bits = e.x;
+    prefix = e.y;
+  } else {
+    bits = c.rank_bits[w];
+    prefix = c.rank_prefix[w];
+  }
+}
 
 // A FilterExec fused below the probe side whose predicate is an AND of `column <op> literal` over fixed-width integer-like columns
 // (Int32 / Date32 / Int64 / UInt8 / UInt32 — TPC-H's date and code filters): the counts pass of the selective probe evaluates it
@@ -367,6 +386,145 @@ __global__ __launch_bounds__(BLOCK) void k_rank_setbits(KeyCol k, int64_t n, uin
     }
   }
 }
+// rank map build for strictly ascending keys with no NULLs, the interleaved table in ONE pass.  Rank equals row there, so the entry
+// of a bitmap word needs nothing from other words: .x = the bits of the rows that fall into it, .y = the row of its first key.
+// A workgroup takes RT_ROWS consecutive rows and OWNS the words whose first key lies among them: it skips its leading keys that
+// share the word of the row just before its first (that word is the previous workgroup's) and reads up to 63 rows past its end
+// to finish its last word.  One writer per word: no global atomics, no zeroed bitmap, no prefix scan.
+// The wave-level run sum of k_rank_setbits costs ~100 vector instructions per 64 lanes, which bounds that kernel, not memory: so a
+// lane takes FOUR consecutive rows here.  The leading keys of a lane that share a word are ORed in registers and enter the wave's
+// run sum as one value; a wave sums the values of each run of lanes that share a word and the run's last lane folds it into an LDS
+// window of RT_WIN words that starts at the workgroup's first word: one LDS OR and one LDS MIN (the run's first row) per run.  The
+// keys of a lane behind its first word change go to the window one by one.  The window then leaves as 16-byte-per-lane stores of
+// consecutive entries.  A key whose word lies beyond the window (a locally sparse stretch of keys) goes to the table directly,
+// which the caller has zeroed: words without a key stay {0, 0} (the contract next to JoinTable::rank_tab).
+// VERIFY: min / max / order are the caller's guess; every own row is compared with its predecessor and the guessed range, a
+// violation raises `flag`.  Keys may be anything then: a key outside the range contributes nothing and every store is bounded by
+// the table's size, so a wrong guess leaves a table that is thrown away, never a write outside it.
+// four consecutive keys from row i0 (a multiple of 4) on, as 16-byte loads where the column's base address allows
+typedef unsigned long long rt_u64x2 __attribute__((ext_vector_type(2)));
+typedef unsigned rt_u32x4 __attribute__((ext_vector_type(4)));
+template <int KT>
+__device__ __forceinline__ void load_keys4(const KeyCol& k, int64_t i0, uint64_t (&out)[4]) {
+  if (KT == KT_I64 && ((uintptr_t)k.data & 15) == 0) {   // (uniform)
+    const rt_u64x2* p = reinterpret_cast<const rt_u64x2*>((const uint64_t*)k.data + i0);
+    const rt_u64x2 a = __builtin_nontemporal_load(p), b = __builtin_nontemporal_load(p + 1);
+    out[0] = a.x; out[1] = a.y; out[2] = b.x; out[3] = b.y;
+  } else if ((KT == KT_I32 || KT == KT_U32) && ((uintptr_t)k.data & 15) == 0) {
+    const rt_u32x4 a = __builtin_nontemporal_load(reinterpret_cast<const rt_u32x4*>((const uint32_t*)k.data + i0));
+    out[0] = KT == KT_I32 ? (uint64_t)(int64_t)(int32_t)a.x : a.x;
+    out[1] = KT == KT_I32 ? (uint64_t)(int64_t)(int32_t)a.y : a.y;
+    out[2] = KT == KT_I32 ? (uint64_t)(int64_t)(int32_t)a.z : a.z;
+    out[3] = KT == KT_I32 ? (uint64_t)(int64_t)(int32_t)a.w : a.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; j++) out[j] = load_key<KT, true>(k, i0 + j);
+  }
+}
+constexpr int RT_ROWS = 4096;                                       // rows per workgroup
+constexpr int RT_WIN = 1024;                                        // words staged in LDS (12 KB): RT_ROWS rows down to a local key density of 1 / 16
+constexpr int RT_LANE_ROWS = 4;                                     // consecutive rows per lane
+constexpr int RT_CHUNK = WAVE * RT_LANE_ROWS;                       // rows per wave and step
+constexpr int RT_STEPS = RT_ROWS / RT_CHUNK / (BLOCK / WAVE);       // steps per wave, all loaded up front
+template <int KT, bool VERIFY>
+__global__ __launch_bounds__(BLOCK) void k_rank_tab_onepass(KeyCol k, int64_t n, uint64_t offset, uint64_t range, ulonglong2* __restrict__ tab, int* __restrict__ flag) {
+  __shared__ unsigned long long s_bits[RT_WIN];
+  __shared__ unsigned s_first[RT_WIN];   // first row of the word, relative to the workgroup's first row
+  constexpr int WAVES = BLOCK / WAVE;
+  const unsigned lane = lane_id();
+  const int wv = threadIdx.x >> 6;
+  const int64_t r0 = (int64_t)blockIdx.x * RT_ROWS;
+  const int64_t r1 = r0 + RT_ROWS < n ? r0 + RT_ROWS : n;
+  const uint64_t n_words = (range >> 6) + 1;
+  uint64_t idx[RT_STEPS][RT_LANE_ROWS], pidx[RT_STEPS];
+#pragma unroll
+  for (int c = 0; c < RT_STEPS; c++) {
+    const int64_t i0 = r0 + (int64_t)(c * WAVES + wv) * RT_CHUNK + lane * RT_LANE_ROWS;
+    if (i0 + RT_LANE_ROWS <= n) {
+      load_keys4<KT>(k, i0, idx[c]);   // (16 bytes per lane and load; the keys stream by once: non-temporal)
+#pragma unroll
+      for (int j = 0; j < RT_LANE_ROWS; j++) idx[c][j] -= offset;
+    } else {
+#pragma unroll
+      for (int j = 0; j < RT_LANE_ROWS; j++) idx[c][j] = load_key<KT, true>(k, i0 + j < n ? i0 + j : n - 1) - offset;
+    }
+    pidx[c] = 0;
+    if (VERIFY) pidx[c] = load_key<KT>(k, i0 < n ? (i0 > 0 ? i0 - 1 : 0) : n - 1) - offset;   // the neighbour's line: a cache hit
+  }
+  // the rows past the end that may finish the last word: one per lane of the last wave
+  const bool tail_lane = wv == WAVES - 1 && r1 + lane < n;
+  const uint64_t tail_idx = tail_lane ? load_key<KT>(k, r1 + lane) - offset : ~0ull;
+  const uint64_t w_first = r0 > 0 ? ((load_key<KT>(k, r0 - 1) - offset) >> 6) + 1 : 0ull;   // the first word this workgroup may own
+  const uint64_t w_last = (load_key<KT>(k, r1 - 1) - offset) >> 6;                           // its last
+  const uint64_t w_end = w_last < n_words ? w_last : n_words - 1;
+  // the words that leave through the window: [w_first, w_first + cnt)
+  const int cnt = w_end < w_first ? 0 : (w_end - w_first + 1 < (uint64_t)RT_WIN ? (int)(w_end - w_first + 1) : RT_WIN);
+  for (int t = threadIdx.x; t < cnt; t += BLOCK) {
+    s_bits[t] = 0ull;
+    s_first[t] = ~0u;
+  }
+  __syncthreads();
+  // one key (or the ORed leading keys of a lane) into its word: `first` = this is the word's first key for certain
+  auto put = [&](uint64_t w, unsigned long long bits, int64_t row, bool first_known, bool is_first) {
+    const uint64_t slot = w - w_first;
+    if (slot < (uint64_t)cnt) {
+      atomicOr(&s_bits[slot], bits);   // (a word's keys may sit in two lanes, two steps, two waves)
+      atomicMin(&s_first[slot], (unsigned)(row - r0));
+    } else {
+      // beyond the window: narrow and scattered, which is what a locally sparse stretch costs; the word's first key is
+      // the one whose predecessor row lies in another word
+      unsigned long long* e = reinterpret_cast<unsigned long long*>(tab + w);
+      (void)__hip_atomic_fetch_or(e, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (!first_known) is_first = row == 0 || ((load_key<KT>(k, row - 1) - offset) >> 6) != w;
+      if (is_first) e[1] = (unsigned long long)row;
+    }
+  };
+#pragma unroll
+  for (int c = 0; c < RT_STEPS; c++) {
+    const int64_t i0 = r0 + (int64_t)(c * WAVES + wv) * RT_CHUNK + lane * RT_LANE_ROWS;
+    bool ok[RT_LANE_ROWS], later[RT_LANE_ROWS];
+    uint64_t w = ~0ull, v = 0ull;   // lanes without a key that counts form their own (ignored) runs
+    unsigned rel = 0;
+    bool found = false, bad = false, any_later = false;
+#pragma unroll
+    for (int j = 0; j < RT_LANE_ROWS; j++) {
+      const uint64_t x = idx[c][j];
+      if (VERIFY) bad = bad || (i0 + j < r1 && (x > range || (i0 + j > 0 && x <= (j ? idx[c][j - 1] : pidx[c]))));
+      ok[j] = i0 + j < r1 && x <= range && (x >> 6) >= w_first;
+      if (ok[j] && !found) {
+        found = true;
+        w = x >> 6;
+        rel = (unsigned)(i0 + j - r0);
+      }
+      const bool lead = ok[j] && (x >> 6) == w;
+      v |= lead ? 1ull << (x & 63) : 0ull;
+      later[j] = ok[j] && !lead;
+      any_later = any_later || later[j];
+    }
+    if (VERIFY && ballot64(bad) != 0 && lane == 0) atomicOr(flag, 1);
+    // ascending keys: the lanes that share a word are contiguous and carry distinct bits, so the word's value over a run of lanes is
+    // S[last lane] - S[lane before the run] of one wave prefix sum (mod 2^64, done with DPP)
+    const uint64_t inc = wave_inclusive_sum_dpp(v);
+    const uint64_t w_next = __shfl_down(w, 1, 64);
+    const uint64_t tails = ballot64(lane == 63 || w_next != w);
+    const uint64_t heads = (tails << 1) | 1ull;
+    const int head_lane = 63 - __builtin_clzll(heads & ((2ull << lane) - 1ull));   // start of this lane's run
+    const uint64_t before = __shfl(inc - v, head_lane, 64);                           // prefix sum ahead of the run
+    const unsigned head_rel = __shfl(rel, head_lane, 64);
+    if (found && ((tails >> lane) & 1ull)) put(w, inc - before, r0 + head_rel, false, false);
+    if (any_later) {
+#pragma unroll
+      for (int j = 1; j < RT_LANE_ROWS; j++)
+        if (later[j]) put(idx[c][j] >> 6, 1ull << (idx[c][j] & 63), i0 + j, true, (idx[c][j - 1] >> 6) != (idx[c][j] >> 6));
+    }
+  }
+  if (tail_lane && tail_idx <= range && (tail_idx >> 6) == w_last && w_last >= w_first) put(w_last, 1ull << (tail_idx & 63), r1 + lane, true, false);
+  __syncthreads();
+  for (int t = threadIdx.x; t < cnt; t += BLOCK) {
+    const unsigned long long b = s_bits[t];
+    tab[w_first + t] = make_ulonglong2(b, b ? (unsigned long long)(r0 + s_first[t]) : 0ull);
+  }
+}
 // rank map build over keys in no order, without atomics: one BYTE per value of the range is set by a plain store (racing stores all
 // write 1; an agent-scope atomic per key — even fire-and-forget — retires at ~27 G/s on this part: 150 M keys = 5.6 ms), then the
 // bytes are packed to the bitmap (pack_bytes_to_bitmap: one ballot per 64 values)
@@ -424,6 +582,9 @@ __global__ __launch_bounds__(RB_THREADS) void k_rank_bits_grouped(const uint64_t
       bits[w0 + i] = w;
     }
   }
+}
+__global__ __launch_bounds__(BLOCK) void k_rank_deinterleave(const ulonglong2* __restrict__ tab, int64_t n_words, uint64_t* __restrict__ bits) {
+  for (int64_t w = (int64_t)blockIdx.x * BLOCK + threadIdx.x; w < n_words; w += (int64_t)gridDim.x * BLOCK) bits[w] = tab[w].x;
 }
 __global__ __launch_bounds__(BLOCK) void k_rank_interleave(const uint64_t* __restrict__ bits, const uint64_t* __restrict__ prefix, int64_t n_words, ulonglong2* __restrict__ tab) {
   for (int64_t w = (int64_t)blockIdx.x * BLOCK + threadIdx.x; w < n_words; w += (int64_t)gridDim.x * BLOCK) tab[w] = make_ulonglong2(bits[w], prefix[w]);
@@ -842,12 +1003,12 @@ __device__ __forceinline__ void hit_words(const ProbeCtx& c, int64_t w0, int64_t
   }
   // the bitmap words alone: 8 useful bytes per 8-byte stride (through rank_tab's {bits, prefix} pairs the same question touched
   // twice the lines — SF300's orders: 450 MB, outside the 256 MB Infinity Cache, against 225 MB inside it)
-  const uint64_t* tab = c.rank_bits;
+  // (a table straight from the one-pass build has no bitmap of its own until a membership pass asks: rank_word)
   uint64_t bits[N];
 #pragma unroll
   for (int j = 0; j < N; j++) {
     ok[j] = ok[j] && idx[j] < c.am_size;
-    bits[j] = tab[ok[j] ? (idx[j] >> 6) : 0];
+    bits[j] = rank_word(c, ok[j] ? (idx[j] >> 6) : 0);
   }
 #pragma unroll
   for (int j = 0; j < N; j++) word[j] = ballot64(ok[j] && ((bits[j] >> (idx[j] & 63)) & 1ull));
@@ -1553,14 +1714,7 @@ __global__ __launch_bounds__(BLOCK) void k_join_emit_listed(ProbeCtx c, JoinCopy
           brow = (int64_t)c.heads[idx] - 1;
         } else {
           uint64_t bw, pre;
-          if (c.rank_tab) {   // (uniform)
-            const ulonglong2 e = c.rank_tab[idx >> 6];
-            bw = e.x;
-            pre = e.y;
-          } else {
-            bw = c.rank_bits[idx >> 6];
-            pre = c.rank_prefix[idx >> 6];
-          }
+          rank_entry(c, idx >> 6, bw, pre);
           const uint32_t rank = (uint32_t)pre + (uint32_t)__popcll(bw & ((1ull << (idx & 63)) - 1ull));
           brow = c.rank_perm ? (int64_t)c.rank_perm[rank] : (int64_t)rank;
         }
@@ -1969,6 +2123,7 @@ static void ensure_rank_tab(JoinTable& jt) {
   if (jt.kind != KIND_RANK) return;
   std::lock_guard<std::mutex> lk(jt.tab_mu);
   if (jt.rank_tab) return;
+  DFGPU_CHECK(jt.rank_bits && jt.rank_prefix, "internal: rank map without a table and without bitmap + prefix");
   Runtime& r = rt();
   const int64_t n_words = (int64_t)((jt.am_size - 1) >> 6) + 1;
   BufPtr tab = make_buf((size_t)n_words * 16);
@@ -1981,6 +2136,27 @@ static void ensure_rank_tab(JoinTable& jt) {
   jt.rank_tab = tab;
   std::lock_guard<std::mutex> lk2(jt.mu);
   jt.info.table_bytes += n_words * 16;
+}
+
+// The mirror of ensure_rank_tab: the bitmap words alone, for a table the one-pass build left without them, made once by the first
+// probe whose membership pass streams every probe key through the bitmap (k_join_tile_counts: half the bytes per line)
+static void ensure_rank_bits(JoinTable& jt) {
+  if (jt.kind != KIND_RANK) return;
+  std::lock_guard<std::mutex> lk(jt.tab_mu);
+  if (jt.rank_bits) return;
+  DFGPU_CHECK(jt.rank_tab != nullptr, "internal: rank map without a table and without bitmap + prefix");
+  Runtime& r = rt();
+  const int64_t n_words = (int64_t)((jt.am_size - 1) >> 6) + 1;
+  BufPtr bits = make_buf((size_t)n_words * 8);
+  {
+    ProfileScope ps("join_build_rank_deinterleave", n_words * 24);
+    k_rank_deinterleave<<<grid_for(n_words, BLOCK), BLOCK, 0, r.stream>>>(jt.rank_tab->as<ulonglong2>(), n_words, bits->as<uint64_t>());
+    DFGPU_HIP(hipGetLastError());
+  }
+  call_epilogue();  // several host threads: complete before another thread's stream reads it (one thread: its stream orders it, no wait)
+  jt.rank_bits = bits;
+  std::lock_guard<std::mutex> lk2(jt.mu);
+  jt.info.table_bytes += n_words * 8;
 }
 
 // rank map over keys that are not in ascending row order: the rank -> row permutation, made once, by the first probe that needs
@@ -2017,9 +2193,13 @@ static ProbeCtx make_ctx(JoinTable& jt, const Table& probe, const std::vector<in
   }
   c.heads = jt.heads ? jt.heads->as<uint32_t>() : nullptr;
   c.next = jt.next ? jt.next->as<uint32_t>() : nullptr;
-  c.rank_tab = jt.rank_tab ? jt.rank_tab->as<ulonglong2>() : nullptr;
-  c.rank_bits = jt.rank_bits ? jt.rank_bits->as<uint64_t>() : nullptr;
-  c.rank_prefix = jt.rank_prefix ? jt.rank_prefix->as<uint64_t>() : nullptr;
+  {
+    std::lock_guard<std::mutex> lk(jt.tab_mu);   // (another probe thread may be making the table or the bitmap just now)
+    c.rank_tab = jt.rank_tab ? jt.rank_tab->as<ulonglong2>() : nullptr;
+    c.rank_bits = jt.rank_bits ? jt.rank_bits->as<uint64_t>() : nullptr;
+    c.rank_prefix = jt.rank_prefix ? jt.rank_prefix->as<uint64_t>() : nullptr;
+    DFGPU_CHECK(jt.kind != KIND_RANK || c.rank_tab || (c.rank_bits && c.rank_prefix), "internal: rank map without a table and without bitmap + prefix");
+  }
   c.rank_perm = need_build_rows && jt.rank_perm ? jt.rank_perm->as<uint32_t>() : nullptr;
   c.am_offset = jt.am_offset;
   c.am_size = jt.am_size;
@@ -2137,7 +2317,7 @@ static std::unique_ptr<JoinTable> join_build_fixed_keys(const Table& build, cons
   // Large builds guess their statistics instead of measuring them first: keys that arrive in ascending order (a primary key in
   // table order: what dbgen, a sorted file or an ordered scan hands over) have min = the first key, max = the last, and a sample of
   // neighbours says whether that is plausible.  The rank map is then built in ONE pass over the keys that verifies the guess on the
-  // way (k_rank_setbits<.., VERIFY>): 150 M keys, 0.31 ms of the step's 9.8.  A wrong guess costs the verifying pass and is
+  // way (k_rank_tab_onepass<.., VERIFY>, below a density of 0.15 k_rank_setbits<.., VERIFY>).  A wrong guess costs the verifying pass and is
   // repaired by the measured path below (`speculate` = false).
   bool speculated = false;
   const bool spec_off = false;
@@ -2228,7 +2408,12 @@ static std::unique_ptr<JoinTable> join_build_fixed_keys(const Table& build, cons
   // profiles/r3_join_shapes.md; probes that do gather build rows pay rank -> perm -> row, within 10 % of ArrayMap's two accesses.)
   constexpr int64_t MALL_BYTES = (int64_t)256 << 20;
 
-  BufPtr flag = make_zero_buf(4);
+  // the 4-byte flag the build kernels raise (a duplicate key, a wrong guess): made by the first path that hands it to a kernel
+  BufPtr flag;
+  auto need_flag = [&]() {
+    if (!flag) flag = make_zero_buf(4);
+    return flag->as<int>();
+  };
   int dup = 0;
   bool flat_wide = false;
   // A build side that `auto` would hand to the LDS radix join once duplicates show up (below) need not build a rank map to see them
@@ -2240,20 +2425,36 @@ static std::unique_ptr<JoinTable> join_build_fixed_keys(const Table& build, cons
     {
       ProfileScope ps("join_build_sample_duplicates", m * 2 * ks.c[0].width);
       with_key_type(ks.c[0].type, [&](auto kt) {
-        k_sample_duplicates<decltype(kt)::value><<<grid_for(2 * m, BLOCK), BLOCK, 0, r.stream>>>(ks.c[0], nb, nb / m, m, table->as<unsigned long long>(), slots - 1, flag->as<int>());
+        k_sample_duplicates<decltype(kt)::value><<<grid_for(2 * m, BLOCK), BLOCK, 0, r.stream>>>(ks.c[0], nb, nb / m, m, table->as<unsigned long long>(), slots - 1, need_flag());
       });
       DFGPU_HIP(hipGetLastError());
     }
     int seen = 0;
-    d2h(&seen, flag->ptr, 4);
+    d2h(&seen, need_flag(), 4);
     if (seen) {
       dup = 1;
       rank_ok = false;
-      DFGPU_HIP(hipMemsetAsync(flag->ptr, 0, 4, r.stream));
+      DFGPU_HIP(hipMemsetAsync(need_flag(), 0, 4, r.stream));
     }
   }
   if (rank_ok) {
     const int64_t n_words = (int64_t)(range >> 6) + 1;
+    // A build side in ascending order that fills its key range densely enough for the probes to look every row's rank up (below 0.15
+    // the selective flavour takes over: membership from the bitmap, ranks of the few listed rows from bitmap + prefix) gets the
+    // interleaved table and nothing else, in one pass over the keys (k_rank_tab_onepass); bitmap and prefix alone wait for a probe
+    // that wants them (ensure_rank_bits).  Every other build makes bitmap + prefix and leaves the table to ensure_rank_tab.
+    BufPtr eager_tab;
+    if (ascending && (double)nb >= 0.15 * ((double)range + 1.0)) {
+      eager_tab = make_zero_buf((size_t)n_words * 16);   // words without a key stay {0, 0}
+      ProfileScope ps("join_build_rank_tab_onepass", nb * ks.c[0].width + n_words * 16);
+      const int g = (int)((nb + RT_ROWS - 1) / RT_ROWS);
+      with_key_type(ks.c[0].type, [&](auto kt) {
+        constexpr int T = decltype(kt)::value;
+        if (speculated) k_rank_tab_onepass<T, true><<<g, BLOCK, 0, r.stream>>>(ks.c[0], nb, (uint64_t)kmin, range, eager_tab->as<ulonglong2>(), need_flag());
+        else k_rank_tab_onepass<T, false><<<g, BLOCK, 0, r.stream>>>(ks.c[0], nb, (uint64_t)kmin, range, eager_tab->as<ulonglong2>(), nullptr);
+      });
+      DFGPU_HIP(hipGetLastError());
+    } else {
     jt->rank_bits = make_zero_buf((size_t)n_words * 8);
     {
       ProfileScope ps("join_build_rank_map", nb * ks.c[0].width);
@@ -2282,7 +2483,7 @@ static std::unique_ptr<JoinTable> join_build_fixed_keys(const Table& build, cons
         h2d_async(d_first->ptr, gfirst.data(), gfirst.size() * 8);
         const size_t lds = (size_t)((max_span >> 6) + 2) * 8;
         DFGPU_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rank_bits_grouped), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        k_rank_bits_grouped<<<P, RB_THREADS, lds, r.stream>>>(gr.keys->as<uint64_t>(), gr.bounds->as<uint64_t>(), d_first->as<uint64_t>(), (uint64_t)kmin, bits, flag->as<int>());
+        k_rank_bits_grouped<<<P, RB_THREADS, lds, r.stream>>>(gr.keys->as<uint64_t>(), gr.bounds->as<uint64_t>(), d_first->as<uint64_t>(), (uint64_t)kmin, bits, need_flag());
         DFGPU_HIP(hipGetLastError());
         DFGPU_HIP(hipStreamSynchronize(r.stream));   // gfirst is a local the copy reads
       } else {
@@ -2314,29 +2515,22 @@ static std::unique_ptr<JoinTable> join_build_fixed_keys(const Table& build, cons
       with_key_type(kc0.type, [&](auto kt) {
         constexpr int T = decltype(kt)::value;
         // ascending implies no NULL keys
-        if (speculated) k_rank_setbits<T, false, true, true><<<g, BLOCK, 0, r.stream>>>(kc0, nb, (uint64_t)kmin, bits, flag->as<int>(), range);
-        else if (ascending) k_rank_setbits<T, false, true><<<g, BLOCK, 0, r.stream>>>(kc0, nb, (uint64_t)kmin, bits, flag->as<int>());
-        else if (kc0.valid) k_rank_setbits<T, true, false><<<g, BLOCK, 0, r.stream>>>(kc0, nb, (uint64_t)kmin, bits, flag->as<int>());
-        else k_rank_setbits<T, false, false><<<g, BLOCK, 0, r.stream>>>(kc0, nb, (uint64_t)kmin, bits, flag->as<int>());
+        if (speculated) k_rank_setbits<T, false, true, true><<<g, BLOCK, 0, r.stream>>>(kc0, nb, (uint64_t)kmin, bits, need_flag(), range);
+        else if (ascending) k_rank_setbits<T, false, true><<<g, BLOCK, 0, r.stream>>>(kc0, nb, (uint64_t)kmin, bits, need_flag());
+        else if (kc0.valid) k_rank_setbits<T, true, false><<<g, BLOCK, 0, r.stream>>>(kc0, nb, (uint64_t)kmin, bits, need_flag());
+        else k_rank_setbits<T, false, false><<<g, BLOCK, 0, r.stream>>>(kc0, nb, (uint64_t)kmin, bits, need_flag());
       });
       }
       }
     }
     jt->rank_prefix = make_buf((size_t)(n_words + 1) * 8);
-    // A build side that fills its key range densely enough for the probes to look every row's rank up (below 0.15 the selective flavour
-    // takes over: membership from the bitmap, ranks of the few listed rows from bitmap + prefix) gets the interleaved table from the
-    // prefix scan's own down-sweep; the others leave it to the first probe that asks (ensure_rank_tab).
-    BufPtr eager_tab;
-    if (ascending && (double)nb >= 0.15 * ((double)range + 1.0) && option_on("join.eager_rank_tab", true)) {
-      eager_tab = make_buf((size_t)n_words * 16);
-      scan_bitmap_words_tab(jt->rank_bits->as<uint64_t>(), n_words, jt->rank_prefix->as<uint64_t>(), eager_tab->ptr);
-    } else
     scan_mask_popcounts(jt->rank_bits->as<uint64_t>(), nullptr, n_words * 64, jt->rank_prefix->as<uint64_t>());
     // keys in no order set their bits without looking: two rows with one key set one bit
     if (!ascending) dup = (int64_t)read_u64(jt->rank_prefix->as<uint64_t>() + n_words) != n_valid_keys;
+    }
     if (speculated) {
       int wrong = 0;
-      d2h(&wrong, flag->ptr, 4);
+      d2h(&wrong, need_flag(), 4);
       if (wrong) {  // not ascending after all (or a key outside [first, last]): measure, then build
         ProfileScope ps("join_build_speculation_missed", 0);
         jt.reset();
@@ -2352,12 +2546,9 @@ static std::unique_ptr<JoinTable> join_build_fixed_keys(const Table& build, cons
       jt->am_size = range + 1;
       jt->rank_needs_perm = !ascending;  // the permutation itself waits for a probe that needs build rows (ensure_rank_perm)
       // (bitmap and prefix stay as they are: the membership-only passes read the bitmap, the listed emit both; the interleaved view
-      // waits for a probe that wants it — ensure_rank_tab — unless the scan above already left it)
+      // waits for a probe that wants it — ensure_rank_tab — unless the one-pass build above left it, and nothing else)
       jt->info.table_bytes = n_words * 16;
-      if (eager_tab) {
-        jt->rank_tab = eager_tab;
-        jt->info.table_bytes += n_words * 16;
-      }
+      jt->rank_tab = eager_tab;
     } else {
       DFGPU_CHECK(opts.table_mode != 3, "rank-map join table requested but the build keys are not unique");
       jt->rank_bits.reset();
@@ -2387,8 +2578,8 @@ static std::unique_ptr<JoinTable> join_build_fixed_keys(const Table& build, cons
       const int g = std::min(grid_for(nb, BLOCK * BUILD_UNROLL), 2048);
       with_key_type(ks.c[0].type, [&](auto kt) {
         constexpr int T = decltype(kt)::value;
-        if (ks.c[0].valid) k_am_build<T, true><<<g, BLOCK, 0, r.stream>>>(ks.c[0], nb, jt->am_offset, jt->heads->as<uint32_t>(), next, flag->as<int>());
-        else k_am_build<T, false><<<g, BLOCK, 0, r.stream>>>(ks.c[0], nb, jt->am_offset, jt->heads->as<uint32_t>(), next, flag->as<int>());
+        if (ks.c[0].valid) k_am_build<T, true><<<g, BLOCK, 0, r.stream>>>(ks.c[0], nb, jt->am_offset, jt->heads->as<uint32_t>(), next, need_flag());
+        else k_am_build<T, false><<<g, BLOCK, 0, r.stream>>>(ks.c[0], nb, jt->am_offset, jt->heads->as<uint32_t>(), next, need_flag());
       });
     };
     // duplicates already known (the rank map saw them): build the chains in the first pass
@@ -2398,7 +2589,7 @@ static std::unique_ptr<JoinTable> join_build_fixed_keys(const Table& build, cons
       am_build(dup ? jt->next->as<uint32_t>() : nullptr);
     }
     if (!dup) {
-      d2h(&dup, flag->ptr, 4);
+      d2h(&dup, need_flag(), 4);
       if (dup && opts.table_mode == 0 && opts.probe_mode == 4 && ks.n == 1 && nb * 8 > MALL_BYTES) {
         // duplicates at a size where the chains would live in HBM, and the plan does not observe the probe order: LDS radix join
         jt->heads.reset();
@@ -2442,15 +2633,15 @@ static std::unique_ptr<JoinTable> join_build_fixed_keys(const Table& build, cons
       ProfileScope ps("join_build_flat_table", kb + nb * 4 + (int64_t)cap * (flat_wide ? 32 : 16));
       if (nb) {
         const int g = grid_for(nb, BLOCK);
-        if (flat_wide) k_flat_claim<true><<<g, BLOCK, 0, r.stream>>>(ks, jt->flat_layout, nb, nen, jt->force_collisions, jt->flat_shift, jt->flat_mask, owner->as<uint32_t>(), jt->next->as<uint32_t>(), flag->as<int>(), more->as<uint32_t>());
-        else k_flat_claim<false><<<g, BLOCK, 0, r.stream>>>(ks, jt->flat_layout, nb, nen, jt->force_collisions, jt->flat_shift, jt->flat_mask, owner->as<uint32_t>(), jt->next->as<uint32_t>(), flag->as<int>(), more->as<uint32_t>());
+        if (flat_wide) k_flat_claim<true><<<g, BLOCK, 0, r.stream>>>(ks, jt->flat_layout, nb, nen, jt->force_collisions, jt->flat_shift, jt->flat_mask, owner->as<uint32_t>(), jt->next->as<uint32_t>(), need_flag(), more->as<uint32_t>());
+        else k_flat_claim<false><<<g, BLOCK, 0, r.stream>>>(ks, jt->flat_layout, nb, nen, jt->force_collisions, jt->flat_shift, jt->flat_mask, owner->as<uint32_t>(), jt->next->as<uint32_t>(), need_flag(), more->as<uint32_t>());
       }
       const int gf = grid_for((int64_t)cap, BLOCK);
       if (flat_wide) k_flat_fill<true><<<gf, BLOCK, 0, r.stream>>>(ks, jt->flat_layout, (int64_t)cap, nen, owner->as<uint32_t>(), more->as<uint32_t>(), jt->flat->as<uint4>());
       else k_flat_fill<false><<<gf, BLOCK, 0, r.stream>>>(ks, jt->flat_layout, (int64_t)cap, nen, owner->as<uint32_t>(), more->as<uint32_t>(), jt->flat->as<uint4>());
       DFGPU_HIP(hipGetLastError());
     }
-    d2h(&dup, flag->ptr, 4);
+    d2h(&dup, need_flag(), 4);
     jt->info.table_bytes = (int64_t)cap * (flat_wide ? 32 : 16) + nb * 4;
   } else if (jt->kind != KIND_RANK) {
     DFGPU_CHECK(opts.table_mode != 5, "flat (inline-key) join table requested but the key columns do not pack into 16 bytes");
@@ -2470,8 +2661,8 @@ static std::unique_ptr<JoinTable> join_build_fixed_keys(const Table& build, cons
                                                                 jt->heads->as<uint32_t>(), jt->next->as<uint32_t>());
       }
       ProfileScope ps("join_build_check_unique", kb + nb * 4);
-      k_hm_check_unique<<<grid_for(nb, BLOCK), BLOCK, 0, r.stream>>>(ks, nb, null_equality == DFGPU_NULL_EQUALS_NULL, jt->next->as<uint32_t>(), flag->as<int>());
-      d2h(&dup, flag->ptr, 4);
+      k_hm_check_unique<<<grid_for(nb, BLOCK), BLOCK, 0, r.stream>>>(ks, nb, null_equality == DFGPU_NULL_EQUALS_NULL, jt->next->as<uint32_t>(), need_flag());
+      d2h(&dup, need_flag(), 4);
     }
     jt->info.table_bytes = (int64_t)cap * 4 + nb * 4;
   }
@@ -2858,6 +3049,12 @@ static Table join_probe(JoinTable& jt, const Table& probe, const std::vector<int
       ctx.rank_tab = jt.rank_tab->as<ulonglong2>();
     }
   };
+  auto need_bits = [&]() {   // a pass that streams every probe key through the bitmap
+    if (jt.kind == KIND_RANK) {
+      ensure_rank_bits(jt);
+      ctx.rank_bits = jt.rank_bits->as<uint64_t>();
+    }
+  };
   for (int c : bout) DFGPU_CHECK(c >= 0 && c < (int)jt.build.cols.size(), "build output column out of range");
   for (int c : pout) DFGPU_CHECK(c >= 0 && c < (int)probe.cols.size(), "probe output column out of range");
   uint8_t* visited = nullptr;
@@ -3186,6 +3383,7 @@ static Table join_probe(JoinTable& jt, const Table& probe, const std::vector<int
       BufPtr counts = make_buf((size_t)n_tiles * 4);
       state = make_buf((size_t)(n_tiles + 1) * 8);
       if (listed) out_words = make_buf((size_t)n_words * 8);
+      if (kind == KIND_RANK) need_bits();
       {
         ProfileScope ps("join_probe_tile_counts", key_bytes + (pred_in_counts ? np * lazy->pred_bytes_per_row : 0));
         with_kind_and_key(kind, ctx.pkeys.c[0].type, [&](auto kd, auto kt) {
