@@ -190,12 +190,26 @@ def lineitem10_float():
     dev.free()
 
 
+def _flags_fsum_reference(host):
+    """{aggregate: {(l_returnflag, l_linestatus): GroupSum}} of the four-group shape: math.fsum per column and group (about 15 M addends
+    each), the expressions as numpy's double arithmetic rounds them (tests/float_sum_ref.py `rounded_rows`: 2 and 4 float operations)"""
+    from tests import float_sum_ref as R
+    rf, ls = host.column("l_returnflag").to_numpy(), host.column("l_linestatus").to_numpy()
+    slices = {(k >> 8, k & 255): idx for k, idx in R.group_slices(rf.astype(np.int64) * 256 + ls).items()}
+    price, disc, tax, qty = (host.column(c).to_numpy() for c in ("l_extendedprice", "l_discount", "l_tax", "l_quantity"))
+    disc_price = price * (1.0 - disc)
+    return {"sum_base_price": R.exact_group_sums(slices, price), "sum_disc_price": R.exact_group_sums(slices, disc_price, k=2),
+            "sum_charge": R.exact_group_sums(slices, disc_price * (1.0 + tax), k=4), "avg_qty": R.exact_group_sums(slices, qty),
+            "avg_disc": R.exact_group_sums(slices, disc)}
+
+
 @pytest.mark.parametrize("group_key", ["flags", "l_orderkey", "dense_bucket", "hashed"])
 def test_sf10_float64_sums_and_averages_within_1e_6(lineitem10_float, evaluator, group_key):
     """Float64 money columns (dfgpu_tpch_lineitem(float_money=1)): SUM / AVG accumulate in whatever order the device's atomics land,
     the oracle in row order — north_star's tolerance is 1e-6 relative.  Four group shapes = the four accumulation paths: 4 groups
     (LDS cells, ~15 M addends per group), one run per order (runs node), a dense integer key in no order (rank interning, 100 003
-    groups), two key columns (hash interning, global atomics)."""
+    groups), two key columns (hash interning, global atomics).  The four-group shape is held to math.fsum and the derived bound of
+    tests/float_sum_ref.py as well."""
     from datafusion_amd import ops
     from datafusion_amd.expr import col, lit
     from oracle import oracle
@@ -222,3 +236,19 @@ def test_sf10_float64_sums_and_averages_within_1e_6(lineitem10_float, evaluator,
             assert rel.max() <= 1e-6, (name, float(rel.max()))
         else:
             assert np.array_equal(g, e), name
+    if group_key != "flags":
+        return
+    # the four-group shape also against the truth: math.fsum, inside the bound every double-precision summation of m = n_g additions keeps
+    # (the largest m anywhere in the suite)
+    from tests import float_sum_ref as R
+    if "flags_fsum" not in lineitem10_float["expected"]:
+        lineitem10_float["expected"]["flags_fsum"] = _flags_fsum_reference(lineitem10_float["host"])
+    keys = list(zip(got.column("l_returnflag").to_pylist(), got.column("l_linestatus").to_pylist()))
+    for name, ref in lineitem10_float["expected"]["flags_fsum"].items():
+        assert set(ref) == set(keys)
+        for key, value, count in zip(keys, got.column(name).to_pylist(), got.column("n").to_pylist()):
+            r = ref[key]
+            assert r.n == count and r.fsum_used                  # (N, F) has 0.4 M rows at SF10, the other groups 14 to 30 M
+            exact, bound = (r.exact_avg(), r.avg_bound()) if name.startswith("avg") else (r.exact, r.sum_bound())
+            print(f"sf10 flags / {evaluator} / {name} / group {key}: |error| / bound = {R.ratio(value, exact, bound):.3g}")
+            assert R.within(value, exact, bound), (evaluator, name, key, value, float(exact), R.ratio(value, exact, bound))
