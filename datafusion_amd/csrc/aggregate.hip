@@ -1382,7 +1382,6 @@ __device__ __forceinline__ void lds_add_limbs(unsigned long long* c, int plane, 
 }
 
 // rows [begin, end) of the input.  LDS: register file (TileProgram) | accumulator cells | seen | keys | first rows.
-template <bool PREFETCH>
 __global__ __launch_bounds__(BLOCK) void k_agg_fused_tile(TileProgram p, int pred_opnd, int key_opnd0, int key_opnd1, SmallAccSet accs, int64_t begin,
                                                          int64_t end, int L, int nrep, uint32_t* __restrict__ g_first, uint32_t* __restrict__ g_seen) {
   extern __shared__ __align__(16) unsigned char s_raw[];
@@ -1407,11 +1406,10 @@ __global__ __launch_bounds__(BLOCK) void k_agg_fused_tile(TileProgram p, int pre
   const int64_t stride = (int64_t)gridDim.x * BLOCK;
   int64_t i = begin + (int64_t)blockIdx.x * BLOCK + threadIdx.x;
   RpRaw raw;
-  if (PREFETCH && i < end) tp_issue_row(p, i, raw);
+  if (i < end) tp_issue_row(p, i, raw);
   for (; i < end; i += stride) {
-    if (!PREFETCH) tp_issue_row(p, i, raw);
     tp_commit_row(p, raw, t);
-    if (PREFETCH && i + stride < end) tp_issue_row(p, i + stride, raw);
+    if (i + stride < end) tp_issue_row(p, i + stride, raw);
     if (pred_opnd >= 0) {
       tp_exec(p, 0, p.n_pred_end, t);
       if (!tp_true(p, t, (uint32_t)pred_opnd)) continue;
@@ -1968,9 +1966,42 @@ static void small_sync_host_keys(Aggregate& A, int ngk) {
     for (int64_t i = 0; i < G0; i++) A.small_keys[(size_t)i] |= (uint16_t)(b[(size_t)i] << (8 * g));
   }
 }
+// The keys a pass met (`first_row[key]` != 0xFFFFFFFF) that have no group yet get the next group numbers in first-seen order
+// (group_values/mod.rs:88-92) and are appended to the host mirror (in step with the groups: small_sync_host_keys).
+// Returns key -> group number (0 for a key without a group).
+static std::vector<uint32_t> small_number_fresh_keys(Aggregate& A, const std::vector<uint32_t>& first_row) {
+  std::vector<uint32_t> gid_of(first_row.size(), 0u);
+  std::vector<bool> known(first_row.size(), false);
+  for (size_t g = 0; g < A.small_keys.size(); g++) {
+    gid_of[A.small_keys[g]] = (uint32_t)g;
+    known[A.small_keys[g]] = true;
+  }
+  std::vector<std::pair<uint32_t, uint32_t>> fresh;  // (first row, key)
+  for (uint32_t k = 0; k < (uint32_t)first_row.size(); k++)
+    if (first_row[k] != 0xFFFFFFFFu && !known[k]) fresh.push_back({first_row[k], k});
+  std::sort(fresh.begin(), fresh.end());
+  for (auto& fk : fresh) {
+    gid_of[fk.second] = (uint32_t)A.small_keys.size();
+    A.small_keys.push_back((uint16_t)fk.second);
+  }
+  return gid_of;
+}
 
 // ---------------------------------------------------------------- runtime-specialised node (jit.hip)
-// Argument block of the generated kernel: the layout below is repeated textually in the generated source.
+// The argument block of each generated kernel (AggNodeArgs, DenseNodeArgs, RunsNodeArgs) is repeated textually in its generated
+// source as `struct Args`.  Every generated source ends with this line: twins that drift apart fail the hiprtc compile instead
+// of reading at wrong offsets.
+static std::string args_size_check(size_t host_bytes, const char* host_struct) {
+  return "static_assert(sizeof(Args) == " + std::to_string(host_bytes) + ", \"Args differs from " + host_struct + " (aggregate.hip)\");\n";
+}
+// every block begins with the two arrays the forest's code reads (rowprog_source_prelude)
+template <typename Args>
+static void set_input_columns(Args& args, const CompiledProgram& cp) {
+  for (int c = 0; c < cp.prog.n_cols; c++) {
+    args.col[c] = cp.prog.col_data[c];
+    args.valid[c] = cp.prog.col_valid[c];
+  }
+}
 struct AggNodeArgs {
   const void* col[RP_MAX_COLS];
   const uint64_t* valid[RP_MAX_COLS];
@@ -1981,23 +2012,15 @@ struct AggNodeArgs {
   int64_t begin, end;
   int L, nrep;
 };
-static_assert(RP_MAX_COLS == 10 && MAX_AGGS == 16, "update the Args struct in agg_node_source");
+static_assert(RP_MAX_COLS == 10 && MAX_AGGS == 16, "update the Args structs in the generated sources");
 
 // HIP source of the single-pass small-domain node for ONE expression forest and accumulator set: the skeleton
 // is k_agg_fused_tile's (local key slots, limb cells, replica fold, key-indexed partials); the interpreter is
 // replaced by the forest's straight-line code and every per-accumulator switch by its one live arm.
 static std::string agg_node_source(const CompiledProgram& cp, const SmallAccSet& accs, const std::vector<int>& acc_val, int key_val0, int key_val1) {
   auto S = [](long long v) { return std::to_string(v); };
-  std::string src;
+  std::string src = rowprog_source_prelude();
   src += R"SRC(
-typedef __int128 i128;
-typedef unsigned __int128 u128;
-typedef unsigned long long U64;
-typedef long long I64;
-typedef unsigned int U32;
-typedef int I32;
-typedef unsigned char U8;
-#define BLOCK 256
 #define LIMB_MASK ((1ull << 43) - 1ull)
 struct Args {
   const void* col[10];
@@ -2010,17 +2033,6 @@ struct Args {
   int L, nrep;
 };
 enum { SUM_I64 = 0, SUM_I128 = 1, SUM_F64 = 2, MIN_I64 = 3, MAX_I64 = 4, COUNT = 5, COUNT_STAR = 6 };
-__device__ __forceinline__ double v2f(i128 x) { return __longlong_as_double((long long)(U64)x); }
-__device__ __forceinline__ i128 f2v(double d) { return (i128)(u128)(U64)__double_as_longlong(d); }
-__device__ __forceinline__ long long f64ord(U64 bits) { long long b = (long long)bits; return b ^ (long long)((U64)(b >> 63) >> 1); }
-__device__ __forceinline__ I32 date32_part(I32 days, int part) {  // device.hpp date32_part
-  const I64 z = (I64)days + 719468, era = (z >= 0 ? z : z - 146096) / 146097, doe = z - era * 146097;
-  const I64 yoe = (doe - doe / 1460 + doe / 36524 - doe / 146096) / 365, doy = doe - (365 * yoe + yoe / 4 - yoe / 100), mp = (5 * doy + 2) / 153;
-  const I64 d = doy - (153 * mp + 2) / 5 + 1, m = mp < 10 ? mp + 3 : mp - 9, y = yoe + era * 400 + (m <= 2 ? 1 : 0);
-  return (I32)(part == 0 ? y : part == 1 ? m : d);
-}
-__device__ __forceinline__ bool kt(i128 v, bool n) { return !n && ((int)v & 1); }
-__device__ __forceinline__ bool kf(i128 v, bool n) { return !n && !((int)v & 1); }
 __device__ __forceinline__ U64 identity_of(int kind) {
   return kind == MIN_I64 ? 0x7fffffffffffffffull : kind == MAX_I64 ? 0x8000000000000000ull : 0ull;
 }
@@ -2167,7 +2179,7 @@ extern "C" __global__ __launch_bounds__(BLOCK) void agg_node(Args a) {
     if (s_key[slot] && s_first[slot] != 0xFFFFFFFFu) atomicMin(&a.g_first[s_key[slot] - 1u], s_first[slot]);
 }
 )SRC";
-  return src;
+  return src + args_size_check(sizeof(AggNodeArgs), "AggNodeArgs");
 }
 
 // ---------------------------------------------------------------- specialised node: one dense integer group key
@@ -2203,49 +2215,8 @@ struct DenseAcc {
   int cell;  // cell word (i128 sums: lo at cell, hi at cell + 1)
 };
 
-static std::string agg_dense_node_source(const CompiledProgram& cp, int key_val, const std::vector<DenseAcc>& accs) {
-  auto S = [](long long v) { return std::to_string(v); };
-  std::string row;  // per-row prologue shared by the three kernels (unused values are dead code in minmax / setbits)
-  row += cp.src_loads;
-  row += cp.src_pred;
-  if (cp.src_pred_val >= 0) row += "    if (N" + S(cp.src_pred_val) + " || !((int)V" + S(cp.src_pred_val) + " & 1)) continue;\n";
-  row += cp.src_outs;
-  row += "    const bool knull = N" + S(key_val) + ";\n    const long long key = (long long)(U64)V" + S(key_val) + ";\n";
-  std::string src = R"SRC(
-typedef __int128 i128;
-typedef unsigned __int128 u128;
-typedef unsigned long long U64;
-typedef long long I64;
-typedef unsigned int U32;
-typedef int I32;
-typedef unsigned char U8;
-#define BLOCK 256
-struct Args {
-  const void* col[10];
-  const U64* valid[10];
-  long long* minmax;
-  U32* flags;
-  U64* bits;
-  const U64* prefix;
-  U32* first_row;
-  U64* cells;
-  U32* seen;
-  long long kmin;
-  long long G;
-  long long null_group;
-  long long begin, end;
-};
-__device__ __forceinline__ double v2f(i128 x) { return __longlong_as_double((long long)(U64)x); }
-__device__ __forceinline__ i128 f2v(double d) { return (i128)(u128)(U64)__double_as_longlong(d); }
-__device__ __forceinline__ long long f64ord(U64 bits) { long long b = (long long)bits; return b ^ (long long)((U64)(b >> 63) >> 1); }
-__device__ __forceinline__ I32 date32_part(I32 days, int part) {  // device.hpp date32_part
-  const I64 z = (I64)days + 719468, era = (z >= 0 ? z : z - 146096) / 146097, doe = z - era * 146097;
-  const I64 yoe = (doe - doe / 1460 + doe / 36524 - doe / 146096) / 365, doy = doe - (365 * yoe + yoe / 4 - yoe / 100), mp = (5 * doy + 2) / 153;
-  const I64 d = doy - (153 * mp + 2) / 5 + 1, m = mp < 10 ? mp + 3 : mp - 9, y = yoe + era * 400 + (m <= 2 ? 1 : 0);
-  return (I32)(part == 0 ? y : part == 1 ? m : d);
-}
-__device__ __forceinline__ bool kt(i128 v, bool n) { return !n && ((int)v & 1); }
-__device__ __forceinline__ bool kf(i128 v, bool n) { return !n && !((int)v & 1); }
+// source text shared by the dense-key and the ordered-runs node (after rowprog_source_prelude)
+static const char* const SEG_SCAN_SOURCE = R"SRC(
 // Segmented inclusive scans over the lanes of a wave: a run = adjacent lanes holding the same group (`head` marks
 // its first lane).  The run's last lane ends up with the run's total, so clustered input issues ONE atomic per run
 // and accumulator instead of one per row.  Every lane of the wave must be executing.
@@ -2277,7 +2248,36 @@ __device__ __forceinline__ long long seg_max_i64(long long v, bool head) {
   SEG_SCAN(const long long o = __shfl_up(v, d, 64); if (lane >= d && !f) v = o > v ? o : v;)
   return v;
 }
+)SRC";
 
+static std::string agg_dense_node_source(const CompiledProgram& cp, int key_val, const std::vector<DenseAcc>& accs) {
+  auto S = [](long long v) { return std::to_string(v); };
+  std::string row;  // per-row prologue shared by the three kernels (unused values are dead code in minmax / setbits)
+  row += cp.src_loads;
+  row += cp.src_pred;
+  if (cp.src_pred_val >= 0) row += "    if (N" + S(cp.src_pred_val) + " || !((int)V" + S(cp.src_pred_val) + " & 1)) continue;\n";
+  row += cp.src_outs;
+  row += "    const bool knull = N" + S(key_val) + ";\n    const long long key = (long long)(U64)V" + S(key_val) + ";\n";
+  std::string src = rowprog_source_prelude();
+  src += R"SRC(
+struct Args {
+  const void* col[10];
+  const U64* valid[10];
+  long long* minmax;
+  U32* flags;
+  U64* bits;
+  const U64* prefix;
+  U32* first_row;
+  U64* cells;
+  U32* seen;
+  long long kmin;
+  long long G;
+  long long null_group;
+  long long begin, end;
+};
+)SRC";
+  src += SEG_SCAN_SOURCE;
+  src += R"SRC(
 extern "C" __global__ __launch_bounds__(BLOCK) void dense_minmax(Args a) {
   long long mn = 0x7fffffffffffffffll, mx = -0x7fffffffffffffffll - 1;
   unsigned any_null = 0u, rows = 0u;
@@ -2411,7 +2411,7 @@ extern "C" __global__ __launch_bounds__(BLOCK) void dense_accumulate(Args a) {
     src += "    }\n";
   }
   src += "    if (tail && (seen & ~a.seen[g])) atomicOr(a.seen + g, seen);\n  }\n}\n";
-  return src;
+  return src + args_size_check(sizeof(DenseNodeArgs), "DenseNodeArgs");
 }
 
 // first rows -> bitmap over row numbers.  Neighbouring groups of clustered input have neighbouring first rows:
@@ -3287,6 +3287,67 @@ static bool fused_general_partitioned(Aggregate& A, const Table& in, const std::
   return general_accumulate_partitioned(ictx, slot_gid, G0, n, accs, G1, row_mask, row_slot);
 }
 
+// ---------------------------------------------------------------- front end shared by the specialised nodes and agg_update_fused
+// Every aggregate's argument becomes an output of `comp`, converted to what its accumulator expects (plan_for): AVG over ints
+// sums f64; MIN/MAX(f64) on the ordered key.  Returns the output per aggregate, -1 = no argument.
+static std::vector<int> compile_agg_arguments(RowProgramCompiler& comp, const Aggregate& A) {
+  std::vector<int> arg_out(A.aggs.size(), -1);
+  for (size_t k = 0; k < A.aggs.size(); k++) {
+    const AggState& a = A.aggs[k];
+    if (!a.has_arg) continue;
+    dfgpu_expr e{a.nodes.data(), (int)a.nodes.size(), a.root};
+    arg_out[k] = comp.add_output(e);
+    dfgpu_field t = comp.output_type(arg_out[k]);
+    if (a.typed) DFGPU_CHECK(a.in_type.type == t.type, "aggregate argument type changed between batches");
+    AccPlan p = plan_for(a.func, t, false);
+    if (p.val == VAL_I32_TO_F64 || p.val == VAL_I64_TO_F64) comp.convert_output(arg_out[k], RP_I2F, t);
+    else if (p.val == VAL_F64_ORDERED) comp.convert_output(arg_out[k], RP_F64ORD, t);
+  }
+  return arg_out;
+}
+// the first batch an update accepts fixes the argument types (the first modification of the state)
+static void fix_argument_types(Aggregate& A, const CompiledProgram& cp, const std::vector<int>& arg_out) {
+  for (size_t k = 0; k < A.aggs.size(); k++) {
+    AggState& a = A.aggs[k];
+    if (!a.typed) {
+      a.in_type = a.has_arg ? cp.out_types[(size_t)arg_out[k]] : fld(DFGPU_INT64);
+      a.typed = true;
+    }
+  }
+}
+// What a node accumulates: one entry per aggregate, and after an AVG's sum the count of its non-NULL arguments.
+struct AccEntry {
+  int agg;            // index into A.aggs
+  bool is_avg_count;
+  int kind;           // AccKind
+  int val;            // the argument's value id in the generated source, -1 = none (COUNT(*))
+  dfgpu_field type;   // the argument's type
+};
+static std::vector<AccEntry> accumulator_entries(const Aggregate& A, const CompiledProgram& cp, const std::vector<int>& arg_out) {
+  std::vector<AccEntry> entries;
+  for (size_t k = 0; k < A.aggs.size(); k++) {
+    const AggState& a = A.aggs[k];
+    const dfgpu_field t = a.typed ? a.in_type : (a.has_arg ? cp.out_types[(size_t)arg_out[k]] : fld(DFGPU_INT64));
+    const int kind = (a.func == DFGPU_AGG_COUNT && !a.has_arg) ? ACC_COUNT_STAR : plan_for(a.func, t, false).kind;
+    const int val = a.has_arg ? cp.src_out_vals[(size_t)arg_out[k]] : -1;
+    entries.push_back({(int)k, false, kind, val, t});
+    if (a.func == DFGPU_AGG_AVG) entries.push_back({(int)k, true, ACC_COUNT, val, t});
+  }
+  return entries;
+}
+// The kernels of one generated source, fetched in the order given.  False when the source does not compile: the caller keeps
+// the interpreter, unless jit.strict makes that an error.
+static bool jit_get_kernels(const std::string& source, std::initializer_list<std::pair<const char*, hipFunction_t*>> kernels) {
+  try {
+    for (const auto& k : kernels) *k.second = jit_get(source, k.first);
+    return true;
+  } catch (const Error& e) {
+    if (option_on("jit.strict", false)) throw;
+    fprintf(stderr, "[dfgpu] node specialisation failed, using the interpreter: %s\n", e.what());
+    return false;
+  }
+}
+
 // The specialised dense-key node.  Returns false (state untouched) when it does not apply.
 static bool agg_update_dense_key_jit(Aggregate& A, const Table& in, const dfgpu_expr* pred) {
   Runtime& r = rt();
@@ -3301,68 +3362,35 @@ static bool agg_update_dense_key_jit(Aggregate& A, const Table& in, const dfgpu_
   const int key_out = comp.add_output(ke);
   const dfgpu_field kf = comp.output_type(key_out);
   if (!(kf.type == DFGPU_INT32 || kf.type == DFGPU_INT64 || kf.type == DFGPU_DATE32 || kf.type == DFGPU_UINT32 || kf.type == DFGPU_UINT8)) return false;
-  std::vector<int> arg_out(A.aggs.size(), -1);
-  for (size_t k = 0; k < A.aggs.size(); k++) {
-    AggState& a = A.aggs[k];
-    if (!a.has_arg) continue;
-    dfgpu_expr e{a.nodes.data(), (int)a.nodes.size(), a.root};
-    arg_out[k] = comp.add_output(e);
-    dfgpu_field t = comp.output_type(arg_out[k]);
-    if (a.typed) DFGPU_CHECK(a.in_type.type == t.type, "aggregate argument type changed between batches");
-    AccPlan p = plan_for(a.func, t, false);
-    if (p.val == VAL_I32_TO_F64 || p.val == VAL_I64_TO_F64) comp.convert_output(arg_out[k], RP_I2F, t);
-    else if (p.val == VAL_F64_ORDERED) comp.convert_output(arg_out[k], RP_F64ORD, t);
-  }
+  const std::vector<int> arg_out = compile_agg_arguments(comp, A);
   CompiledProgram cp;
   if (!comp.finish(cp, why)) return false;
-  // ---- accumulator cells
+  // ---- accumulator cells: entries with the same kind and value share one accumulator
   struct Ent { int agg; bool is_avg_count; int kind; int cell; int seen_bit; };
   std::vector<Ent> entries;
   std::vector<DenseAcc> accs;
   std::vector<int> cell_kind, acc_col, acc_val, acc_agg;   // per accumulator: its argument's input column (-1 none, -2 an expression), ValKind, aggregate
-  for (size_t k = 0; k < A.aggs.size(); k++) {
-    AggState& a = A.aggs[k];
-    dfgpu_field t = a.typed ? a.in_type : (a.has_arg ? cp.out_types[(size_t)arg_out[k]] : fld(DFGPU_INT64));
-    AccPlan pl = plan_for(a.func, t, false);
-    const int kind = (a.func == DFGPU_AGG_COUNT && !a.has_arg) ? ACC_COUNT_STAR : pl.kind;
-    const int val = a.has_arg ? cp.src_out_vals[(size_t)arg_out[k]] : -1;
-    int arg_col = -1;
-    const int acc_column = !a.has_arg ? -1 : (is_plain_column(a.nodes, a.root, &arg_col) ? arg_col : -2);
-    auto unique = [&](int kd) {
-      for (size_t u = 0; u < accs.size(); u++)
-        if (accs[u].kind == kd && accs[u].val == val) return (int)u;
-      accs.push_back({kd, val, (int)cell_kind.size()});
-      acc_col.push_back(acc_column);
-      acc_val.push_back(pl.val);
-      acc_agg.push_back((int)k);
-      cell_kind.push_back(kd == ACC_SUM_I128 ? ACC_SUM_I64 : kd);
-      if (kd == ACC_SUM_I128) cell_kind.push_back(ACC_SUM_I64);
-      return (int)accs.size() - 1;
-    };
-    int u = unique(kind);
-    entries.push_back({(int)k, false, kind, accs[(size_t)u].cell, u});
-    if (a.func == DFGPU_AGG_AVG) {
-      int uc = unique(ACC_COUNT);
-      entries.push_back({(int)k, true, ACC_COUNT, accs[(size_t)uc].cell, uc});
+  for (const AccEntry& en : accumulator_entries(A, cp, arg_out)) {
+    const AggState& a = A.aggs[(size_t)en.agg];
+    int u = 0;
+    while (u < (int)accs.size() && !(accs[(size_t)u].kind == en.kind && accs[(size_t)u].val == en.val)) u++;
+    if (u == (int)accs.size()) {
+      int arg_col = -1;
+      accs.push_back({en.kind, en.val, (int)cell_kind.size()});
+      acc_col.push_back(!a.has_arg ? -1 : (is_plain_column(a.nodes, a.root, &arg_col) ? arg_col : -2));
+      acc_val.push_back(plan_for(a.func, en.type, false).val);
+      acc_agg.push_back(en.agg);
+      cell_kind.push_back(en.kind == ACC_SUM_I128 ? ACC_SUM_I64 : en.kind);
+      if (en.kind == ACC_SUM_I128) cell_kind.push_back(ACC_SUM_I64);
     }
+    entries.push_back({en.agg, en.is_avg_count, en.kind, accs[(size_t)u].cell, u});
   }
   if (accs.size() > 32 || entries.size() > (size_t)MAX_AGGS) return false;
   const std::string source = agg_dense_node_source(cp, cp.src_out_vals[(size_t)key_out], accs);
   hipFunction_t f_minmax = nullptr, f_setbits = nullptr, f_acc = nullptr;
-  try {
-    f_minmax = jit_get(source, "dense_minmax");
-    f_setbits = jit_get(source, "dense_setbits");
-    f_acc = jit_get(source, "dense_accumulate");
-  } catch (const Error& e) {
-    if (option_on("jit.strict", false)) throw;
-    fprintf(stderr, "[dfgpu] node specialisation failed, using the interpreter: %s\n", e.what());
-    return false;
-  }
+  if (!jit_get_kernels(source, {{"dense_minmax", &f_minmax}, {"dense_setbits", &f_setbits}, {"dense_accumulate", &f_acc}})) return false;
   DenseNodeArgs args{};
-  for (int c = 0; c < cp.prog.n_cols; c++) {
-    args.col[c] = cp.prog.col_data[c];
-    args.valid[c] = cp.prog.col_valid[c];
-  }
+  set_input_columns(args, cp);
   args.begin = 0;
   args.end = n;
   const int grid = grid_for(n, BLOCK);
@@ -3409,13 +3437,7 @@ static bool agg_update_dense_key_jit(Aggregate& A, const Table& in, const dfgpu_
   // dense enough: at most 64 bitmap bits per input row (the join's rank-map gate), and a bounded bitmap
   if (range > (1ull << 36) || range > (uint64_t)n * 64) return false;
   // ---- from here on state is modified
-  for (size_t k = 0; k < A.aggs.size(); k++) {
-    AggState& a = A.aggs[k];
-    if (!a.typed) {
-      a.in_type = a.has_arg ? cp.out_types[(size_t)arg_out[k]] : fld(DFGPU_INT64);
-      a.typed = true;
-    }
-  }
+  fix_argument_types(A, cp, arg_out);
   const int64_t n_words = (int64_t)((range + 63) / 64) + 1;
   BufPtr bits = make_zero_buf((size_t)n_words * 8);
   BufPtr prefix = make_buf((size_t)(n_words + 1) * 8);
@@ -3670,15 +3692,8 @@ struct RunsAcc {
 static std::string agg_runs_node_source(const CompiledProgram& cp, int key_val, int key_type, const std::vector<RunsAcc>& accs) {
   auto S = [](long long v) { return std::to_string(v); };
   const int K = (int)accs.size();
-  std::string src = R"SRC(
-typedef __int128 i128;
-typedef unsigned __int128 u128;
-typedef unsigned long long U64;
-typedef long long I64;
-typedef unsigned int U32;
-typedef int I32;
-typedef unsigned char U8;
-#define BLOCK 256
+  std::string src = rowprog_source_prelude();
+  src += R"SRC(
 struct Args {
   const void* col[10];
   const U64* valid[10];
@@ -3689,45 +3704,9 @@ struct Args {
   void* key_out;
   long long n;
 };
-__device__ __forceinline__ double v2f(i128 x) { return __longlong_as_double((long long)(U64)x); }
-__device__ __forceinline__ i128 f2v(double d) { return (i128)(u128)(U64)__double_as_longlong(d); }
-__device__ __forceinline__ long long f64ord(U64 bits) { long long b = (long long)bits; return b ^ (long long)((U64)(b >> 63) >> 1); }
-__device__ __forceinline__ I32 date32_part(I32 days, int part) {  // device.hpp date32_part
-  const I64 z = (I64)days + 719468, era = (z >= 0 ? z : z - 146096) / 146097, doe = z - era * 146097;
-  const I64 yoe = (doe - doe / 1460 + doe / 36524 - doe / 146096) / 365, doy = doe - (365 * yoe + yoe / 4 - yoe / 100), mp = (5 * doy + 2) / 153;
-  const I64 d = doy - (153 * mp + 2) / 5 + 1, m = mp < 10 ? mp + 3 : mp - 9, y = yoe + era * 400 + (m <= 2 ? 1 : 0);
-  return (I32)(part == 0 ? y : part == 1 ? m : d);
-}
-__device__ __forceinline__ bool kt(i128 v, bool n) { return !n && ((int)v & 1); }
-__device__ __forceinline__ bool kf(i128 v, bool n) { return !n && !((int)v & 1); }
-#define SEG_SCAN(STEP)                                        \
-  bool f = head;                                              \
-  const int lane = threadIdx.x & 63;                          \
-  _Pragma("unroll") for (int d = 1; d < 64; d <<= 1) {        \
-    const int fo = __shfl_up((int)f, d, 64);                  \
-    STEP                                                      \
-    if (lane >= d && !f) f = fo != 0;                         \
-  }
-__device__ __forceinline__ U64 seg_add_u64(U64 v, bool head) {
-  SEG_SCAN(const U64 o = __shfl_up(v, d, 64); if (lane >= d && !f) v += o;)
-  return v;
-}
-__device__ __forceinline__ u128 seg_add_u128(u128 v, bool head) {
-  SEG_SCAN(const U64 ol = __shfl_up((U64)v, d, 64); const U64 oh = __shfl_up((U64)(v >> 64), d, 64); if (lane >= d && !f) v += ((u128)oh << 64) | ol;)
-  return v;
-}
-__device__ __forceinline__ double seg_add_f64(double v, bool head) {
-  SEG_SCAN(const double o = __shfl_up(v, d, 64); if (lane >= d && !f) v += o;)
-  return v;
-}
-__device__ __forceinline__ long long seg_min_i64(long long v, bool head) {
-  SEG_SCAN(const long long o = __shfl_up(v, d, 64); if (lane >= d && !f) v = o < v ? o : v;)
-  return v;
-}
-__device__ __forceinline__ long long seg_max_i64(long long v, bool head) {
-  SEG_SCAN(const long long o = __shfl_up(v, d, 64); if (lane >= d && !f) v = o > v ? o : v;)
-  return v;
-}
+)SRC";
+  src += SEG_SCAN_SOURCE;
+  src += R"SRC(
 // Unsegmented inclusive wave prefix sums in 6 DPP steps (VALU only — the segmented scans above cost 3-5 LDS-crossbar
 // permutes per step): a run's total is P[last lane] - P[lane before its first lane], exact in wrapping integer arithmetic.
 template <int CTRL, int ROW_MASK>
@@ -3898,7 +3877,7 @@ extern "C" __global__ __launch_bounds__(BLOCK) void runs_accumulate(Args a) {
     src += "    }\n";
   }
   src += "  }\n}\n";
-  return src;
+  return src + args_size_check(sizeof(RunsNodeArgs), "RunsNodeArgs");
 }
 
 // The ordered-input node.  Returns false (state untouched) when it does not apply.
@@ -3927,48 +3906,21 @@ static bool agg_update_sorted_runs_jit(Aggregate& A, const Table& in, const dfgp
   RowProgramCompiler comp(in);
   dfgpu_expr ke{A.group_nodes[0].data(), (int)A.group_nodes[0].size(), A.group_roots[0]};
   const int key_out = comp.add_output(ke);
-  std::vector<int> arg_out(A.aggs.size(), -1);
-  for (size_t k = 0; k < A.aggs.size(); k++) {
-    AggState& a = A.aggs[k];
-    if (!a.has_arg) continue;
-    dfgpu_expr e{a.nodes.data(), (int)a.nodes.size(), a.root};
-    arg_out[k] = comp.add_output(e);
-    dfgpu_field t = comp.output_type(arg_out[k]);
-    if (a.typed) DFGPU_CHECK(a.in_type.type == t.type, "aggregate argument type changed between batches");
-    AccPlan p = plan_for(a.func, t, false);
-    if (p.val == VAL_I32_TO_F64 || p.val == VAL_I64_TO_F64) comp.convert_output(arg_out[k], RP_I2F, t);
-    else if (p.val == VAL_F64_ORDERED) comp.convert_output(arg_out[k], RP_F64ORD, t);
-  }
+  const std::vector<int> arg_out = compile_agg_arguments(comp, A);
   CompiledProgram cp;
   if (!comp.finish(cp, why)) return false;
-  // ---- accumulators: one per aggregate (+ the row count of an AVG); every run writes its own cells, nothing is shared
-  struct Ent { int agg; bool is_avg_count; int kind; };
-  std::vector<Ent> entries;
+  // ---- accumulators: one per entry; every run writes its own cells, nothing is shared
+  const std::vector<AccEntry> entries = accumulator_entries(A, cp, arg_out);
   std::vector<RunsAcc> accs;
-  for (size_t k = 0; k < A.aggs.size(); k++) {
-    AggState& a = A.aggs[k];
-    dfgpu_field t = a.typed ? a.in_type : (a.has_arg ? cp.out_types[(size_t)arg_out[k]] : fld(DFGPU_INT64));
-    AccPlan pl = plan_for(a.func, t, false);
-    const int kind = (a.func == DFGPU_AGG_COUNT && !a.has_arg) ? ACC_COUNT_STAR : pl.kind;
-    const int val = a.has_arg ? cp.src_out_vals[(size_t)arg_out[k]] : -1;
-    entries.push_back({(int)k, false, kind});
-    accs.push_back({kind, val, kind == ACC_SUM_I128 && t.type == DFGPU_DECIMAL128 && t.precision > 0 && t.precision <= 16,
-                    kind == ACC_SUM_I128 && a.func == DFGPU_AGG_SUM && t.type == DFGPU_DECIMAL128});
-    if (a.func == DFGPU_AGG_AVG) {
-      entries.push_back({(int)k, true, ACC_COUNT});
-      accs.push_back({ACC_COUNT, val, false, false});
-    }
+  for (const AccEntry& en : entries) {
+    const dfgpu_field& t = en.type;
+    accs.push_back({en.kind, en.val, en.kind == ACC_SUM_I128 && t.type == DFGPU_DECIMAL128 && t.precision > 0 && t.precision <= 16,
+                    en.kind == ACC_SUM_I128 && A.aggs[(size_t)en.agg].func == DFGPU_AGG_SUM && t.type == DFGPU_DECIMAL128});
   }
   if (accs.size() > (size_t)RUNS_MAX_ACCS) return false;
   const std::string source = agg_runs_node_source(cp, cp.src_out_vals[(size_t)key_out], kf.type, accs);
   hipFunction_t f_acc = nullptr;
-  try {
-    f_acc = jit_get(source, "runs_accumulate");
-  } catch (const Error& e) {
-    if (option_on("jit.strict", false)) throw;
-    fprintf(stderr, "[dfgpu] node specialisation failed, using the interpreter: %s\n", e.what());
-    return false;
-  }
+  if (!jit_get_kernels(source, {{"runs_accumulate", &f_acc}})) return false;
   // ---- run heads -> group numbers
   const int64_t n_words = (n + 63) / 64;
   BufPtr heads = make_buf((size_t)n_words * 8);
@@ -4009,21 +3961,12 @@ static bool agg_update_sorted_runs_jit(Aggregate& A, const Table& in, const dfgp
   if (flags[1]) return false;  // the runs of the first key are not the groups: the hash path
   const uint32_t has_long = flags[0];
   // ---- from here on state is modified
-  for (size_t k = 0; k < A.aggs.size(); k++) {
-    AggState& a = A.aggs[k];
-    if (!a.typed) {
-      a.in_type = a.has_arg ? cp.out_types[(size_t)arg_out[k]] : fld(DFGPU_INT64);
-      a.typed = true;
-    }
-  }
+  fix_argument_types(A, cp, arg_out);
   grow_accumulators(A, 0, G, /*init=*/has_long != 0);  // plain stores cover every cell unless some run needs the atomics
   Column kc = alloc_like(kcol, G);
   kc.name = A.group_names[0];
   RunsNodeArgs args{};
-  for (int c = 0; c < cp.prog.n_cols; c++) {
-    args.col[c] = cp.prog.col_data[c];
-    args.valid[c] = cp.prog.col_valid[c];
-  }
+  set_input_columns(args, cp);
   args.heads = heads->as<uint64_t>();
   args.prefix = prefix->as<uint64_t>();
   args.key_out = kc.data->ptr;
@@ -4102,27 +4045,17 @@ static bool agg_update_small_single_pass(Aggregate& A, const Table& in, const Co
   const size_t regfile = tile_regfile_bytes(T.n_wide, T.n_narrow);
   if (regfile + 4096 > TILE_LDS_BUDGET) return false;
   // ---- accumulator entries and their LDS cells
-  struct Entry { int agg; bool is_avg_count; int kind; int opnd; int val; };
-  std::vector<Entry> entries;
-  for (size_t k = 0; k < A.aggs.size(); k++) {
-    AggState& a = A.aggs[k];
-    dfgpu_field t = a.typed ? a.in_type : (a.has_arg ? cp.out_types[arg_out[k]] : fld(DFGPU_INT64));
-    AccPlan pl = plan_for(a.func, t, false);
-    int kind = (a.func == DFGPU_AGG_COUNT && !a.has_arg) ? ACC_COUNT_STAR : pl.kind;
-    int opnd = a.has_arg ? cp.tile_outs[arg_out[k]] : -1;
-    int val = a.has_arg ? cp.src_out_vals[arg_out[k]] : -1;
-    entries.push_back({(int)k, false, kind, opnd, val});
-    if (a.func == DFGPU_AGG_AVG) entries.push_back({(int)k, true, ACC_COUNT, opnd, val});
-  }
+  const std::vector<AccEntry> entries = accumulator_entries(A, cp, arg_out);
   DFGPU_CHECK((int)entries.size() <= MAX_AGGS, "too many aggregates for one GPU aggregate node");
   SmallAccSet accs{};
   std::vector<int> src_of(entries.size(), -1);  // entry -> unique accumulator: SUM(x) and AVG(x) share one sum
   std::vector<int> acc_val;                     // unique accumulator -> value id in the generated source
   int ncell = 0;
   for (size_t ei = 0; ei < entries.size(); ei++) {
-    const Entry& e = entries[ei];
+    const AccEntry& e = entries[ei];
+    const int opnd = arg_out[(size_t)e.agg] >= 0 ? cp.tile_outs[(size_t)arg_out[(size_t)e.agg]] : -1;  // the argument's tile operand
     for (int u = 0; u < accs.n && src_of[ei] < 0; u++)
-      if (accs.a[u].kind == e.kind && accs.a[u].reg == e.opnd) src_of[ei] = u;
+      if (accs.a[u].kind == e.kind && accs.a[u].reg == opnd) src_of[ei] = u;
     if (src_of[ei] >= 0) continue;
     const int w = e.kind == ACC_SUM_I128 ? 3 : 1;
     if (ncell + w > SM_MAX_CELLS) return false;
@@ -4130,7 +4063,7 @@ static bool agg_update_small_single_pass(Aggregate& A, const Table& in, const Co
     acc_val.push_back(e.val);
     SmallAcc& d = accs.a[accs.n++];
     d.kind = (int16_t)e.kind;
-    d.reg = (int16_t)e.opnd;
+    d.reg = (int16_t)opnd;
     d.cell0 = (int16_t)ncell;
     for (int j = 0; j < w; j++) accs.cell_kind[ncell + j] = (uint8_t)(e.kind == ACC_SUM_I128 ? ACC_SUM_I64 : e.kind);
     ncell += w;
@@ -4176,22 +4109,14 @@ static bool agg_update_small_single_pass(Aggregate& A, const Table& in, const Co
     return st;
   };
   const int ko0 = ngk > 0 ? cp.tile_outs[key_out[0]] : -1, ko1 = ngk > 1 ? cp.tile_outs[key_out[1]] : -1;
-  const bool prefetch = true;
-  DFGPU_HIP(hipFuncSetAttribute((const void*)k_agg_fused_tile<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TILE_LDS_BUDGET));
-  DFGPU_HIP(hipFuncSetAttribute((const void*)k_agg_fused_tile<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TILE_LDS_BUDGET));
+  DFGPU_HIP(hipFuncSetAttribute((const void*)k_agg_fused_tile, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TILE_LDS_BUDGET));
 
   // large inputs run the node specialised for this forest (jit.hip); DFGPU_JIT=0 keeps the interpreter
   const int64_t jit_min_rows = option_int("jit.min_rows", policy().rows_worth_a_pass());
   const int plane_max_jit = (int)std::min<size_t>((TILE_LDS_BUDGET - 2048) / plane_bytes, 4096);
   hipFunction_t jit_fn = nullptr;
-  if (option_on("jit", true) && n >= jit_min_rows) {
-    try {
-      jit_fn = jit_get(agg_node_source(cp, accs, acc_val, ngk > 0 ? cp.src_out_vals[key_out[0]] : -1, ngk > 1 ? cp.src_out_vals[key_out[1]] : -1), "agg_node");
-    } catch (const Error& e) {
-      if (option_on("jit.strict", false)) throw;
-      fprintf(stderr, "[dfgpu] node specialisation failed, using the interpreter: %s\n", e.what());
-    }
-  }
+  if (option_on("jit", true) && n >= jit_min_rows)
+    jit_get_kernels(agg_node_source(cp, accs, acc_val, ngk > 0 ? cp.src_out_vals[key_out[0]] : -1, ngk > 1 ? cp.src_out_vals[key_out[1]] : -1), {{"agg_node", &jit_fn}});
 
   // launch half: ONE reset kernel (identities of every partial, first-row and seen words) and the node's kernel over [begin, end).
   // `groups_known` = the number of groups the local tables are sized for (0: unknown, 16 slots)
@@ -4215,10 +4140,7 @@ static bool agg_update_small_single_pass(Aggregate& A, const Table& in, const Co
     if (use_jit) {
       ProfileScope ps("agg_fused_jit", m * cp.input_bytes_per_row);
       AggNodeArgs args{};
-      for (int c = 0; c < T.n_cols; c++) {
-        args.col[c] = T.col_data[c];
-        args.valid[c] = T.col_valid[c];
-      }
+      set_input_columns(args, cp);
       for (int k = 0; k < st.accs.n; k++) {
         args.tmp_lo[k] = st.accs.a[k].tmp_lo;
         args.tmp_hi[k] = st.accs.a[k].tmp_hi;
@@ -4233,8 +4155,7 @@ static bool agg_update_small_single_pass(Aggregate& A, const Table& in, const Co
     } else {
       ProfileScope ps("agg_fused_tile", m * cp.input_bytes_per_row);
       const size_t lds = regfile + cell_bytes;
-      if (prefetch) k_agg_fused_tile<true><<<grid, BLOCK, lds, r.stream>>>(T, cp.tile_pred, ko0, ko1, st.accs, begin, end, L, nrep, st.g_first->as<uint32_t>(), st.g_seen->as<uint32_t>());
-      else k_agg_fused_tile<false><<<grid, BLOCK, lds, r.stream>>>(T, cp.tile_pred, ko0, ko1, st.accs, begin, end, L, nrep, st.g_first->as<uint32_t>(), st.g_seen->as<uint32_t>());
+      k_agg_fused_tile<<<grid, BLOCK, lds, r.stream>>>(T, cp.tile_pred, ko0, ko1, st.accs, begin, end, L, nrep, st.g_first->as<uint32_t>(), st.g_seen->as<uint32_t>());
       DFGPU_HIP(hipGetLastError());
     }
   };
@@ -4254,22 +4175,13 @@ static bool agg_update_small_single_pass(Aggregate& A, const Table& in, const Co
       A.ngroups = 1;  // AggregateStream: one output row even for empty input
     } else {
       small_sync_host_keys(A, ngk);
-      std::vector<int64_t> gid_of((size_t)D, -1);
-      for (int64_t g = 0; g < G0; g++) gid_of[A.small_keys[(size_t)g]] = g;
-      std::vector<std::pair<uint32_t, uint32_t>> fresh;  // (first row, key)
-      for (uint32_t k = 0; k < (uint32_t)D; k++)
-        if (hfirst[k] != 0xFFFFFFFFu && gid_of[k] < 0) fresh.push_back({hfirst[k], k});
-      std::sort(fresh.begin(), fresh.end());  // first-seen order (group_values/mod.rs:88-92)
-      for (auto& fk : fresh) {
-        gid_of[fk.second] = (int64_t)A.small_keys.size();
-        A.small_keys.push_back((uint16_t)fk.second);
-      }
+      const std::vector<uint32_t> gid_of = small_number_fresh_keys(A, hfirst);
       for (uint32_t k = 0; k < (uint32_t)D; k++)
         if (hfirst[k] != 0xFFFFFFFFu) {
           touched_keys.push_back(k);
-          touched_gids.push_back((uint32_t)gid_of[k]);
+          touched_gids.push_back(gid_of[k]);
         }
-      if (!fresh.empty() || (int)A.group_keys.cols.size() != ngk) small_rebuild_group_keys(A, in, small_cols);
+      if ((int64_t)A.small_keys.size() != G0 || (int)A.group_keys.cols.size() != ngk) small_rebuild_group_keys(A, in, small_cols);
       A.ngroups = (int64_t)A.small_keys.size();
     }
     const int64_t G1 = A.ngroups;
@@ -4280,7 +4192,7 @@ static bool agg_update_small_single_pass(Aggregate& A, const Table& in, const Co
       MergeDst dst{};
       dst.n = (int)entries.size();
       for (int ei = 0; ei < dst.n; ei++) {
-        const Entry& e = entries[(size_t)ei];
+        const AccEntry& e = entries[(size_t)ei];
         AggState& a = A.aggs[(size_t)e.agg];
         dst.src[ei] = src_of[(size_t)ei];
         if (e.is_avg_count) {
@@ -4377,19 +4289,7 @@ static bool agg_update_fused(Aggregate& A, const Table& in, const dfgpu_expr* pr
       dfgpu_expr e{A.group_nodes[g].data(), (int)A.group_nodes[g].size(), A.group_roots[g]};
       key_out[g] = comp.add_output(e);
     }
-  std::vector<int> arg_out(A.aggs.size(), -1);
-  for (size_t k = 0; k < A.aggs.size(); k++) {
-    AggState& a = A.aggs[k];
-    if (!a.has_arg) continue;
-    dfgpu_expr e{a.nodes.data(), (int)a.nodes.size(), a.root};
-    arg_out[k] = comp.add_output(e);
-    dfgpu_field t = comp.output_type(arg_out[k]);
-    if (a.typed) DFGPU_CHECK(a.in_type.type == t.type, "aggregate argument type changed between batches");
-    // conversions the accumulator expects (plan_for): AVG over ints sums f64; MIN/MAX(f64) on the ordered key
-    AccPlan p = plan_for(a.func, t, false);
-    if (p.val == VAL_I32_TO_F64 || p.val == VAL_I64_TO_F64) comp.convert_output(arg_out[k], RP_I2F, t);
-    else if (p.val == VAL_F64_ORDERED) comp.convert_output(arg_out[k], RP_F64ORD, t);
-  }
+  const std::vector<int> arg_out = compile_agg_arguments(comp, A);
   CompiledProgram cp;
   if (!comp.finish(cp, why)) return false;
 
@@ -4406,13 +4306,7 @@ static bool agg_update_fused(Aggregate& A, const Table& in, const dfgpu_expr* pr
   }
 
   // ---- from here on state is modified
-  for (size_t k = 0; k < A.aggs.size(); k++) {
-    AggState& a = A.aggs[k];
-    if (!a.typed) {
-      a.in_type = a.has_arg ? cp.out_types[arg_out[k]] : fld(DFGPU_INT64);
-      a.typed = true;
-    }
-  }
+  fix_argument_types(A, cp, arg_out);
   if (gid_mode != GID_HASH &&
       agg_update_small_single_pass(A, in, cp, small_cols, key_out, arg_out))
     return true;
@@ -4427,15 +4321,7 @@ static bool agg_update_fused(Aggregate& A, const Table& in, const dfgpu_expr* pr
   if (gid_mode == GID_NONE) {
     G1 = 1;
   } else if (gid_mode == GID_SMALL) {
-    // host mirror of the existing groups' keys
-    if ((int64_t)A.small_keys.size() != G0) {
-      A.small_keys.assign((size_t)G0, 0);
-      for (int g = 0; g < ngk && G0; g++) {
-        std::vector<uint8_t> b((size_t)G0);
-        d2h(b.data(), A.group_keys.cols[g].ptr(), (size_t)G0);
-        for (int64_t i = 0; i < G0; i++) A.small_keys[(size_t)i] |= (uint16_t)(b[(size_t)i] << (8 * g));
-      }
-    }
+    small_sync_host_keys(A, ngk);
     BufPtr first = make_buf((size_t)SMALL_DOMAIN * 4);
     DFGPU_HIP(hipMemsetAsync(first->ptr, 0xFF, (size_t)SMALL_DOMAIN * 4, r.stream));
     {
@@ -4447,20 +4333,7 @@ static bool agg_update_fused(Aggregate& A, const Table& in, const dfgpu_expr* pr
     }
     std::vector<uint32_t> hfirst((size_t)SMALL_DOMAIN);
     d2h(hfirst.data(), first->ptr, (size_t)SMALL_DOMAIN * 4);
-    std::vector<uint32_t> table((size_t)SMALL_DOMAIN, 0u);
-    std::vector<bool> known((size_t)SMALL_DOMAIN, false);
-    for (int64_t gidx = 0; gidx < G0; gidx++) {
-      table[A.small_keys[(size_t)gidx]] = (uint32_t)gidx;
-      known[A.small_keys[(size_t)gidx]] = true;
-    }
-    std::vector<std::pair<uint32_t, uint32_t>> fresh;  // (first row, key)
-    for (uint32_t k = 0; k < (uint32_t)SMALL_DOMAIN; k++)
-      if (hfirst[k] != 0xFFFFFFFFu && !known[k]) fresh.push_back({hfirst[k], k});
-    std::sort(fresh.begin(), fresh.end());  // first-seen order (group_values/mod.rs:88-92)
-    for (auto& fk : fresh) {
-      table[fk.second] = (uint32_t)A.small_keys.size();
-      A.small_keys.push_back((uint16_t)fk.second);
-    }
+    const std::vector<uint32_t> table = small_number_fresh_keys(A, hfirst);
     G1 = (int64_t)A.small_keys.size();
     gid_table = make_buf((size_t)SMALL_DOMAIN * 4);
     h2d_async(gid_table->ptr, table.data(), (size_t)SMALL_DOMAIN * 4);

@@ -400,12 +400,6 @@ hipFunction_t jit_get(const std::string& source, const char* kernel_name);
 // launches on the library stream; `args` is the kernel's single by-value argument struct
 void jit_launch(hipFunction_t fn, int grid, int block, size_t lds_bytes, void* args, size_t args_bytes);
 
-// ----------------------------------------------------------------- runtime specialisation (jit.hip)
-// compiles `source` with hiprtc for gfx950 (cached per process by source text) and returns `kernel_name`
-hipFunction_t jit_get(const std::string& source, const char* kernel_name);
-// launches on the library stream; `args` is the kernel's single by-value argument struct
-void jit_launch(hipFunction_t fn, int grid, int block, size_t lds_bytes, void* args, size_t args_bytes);
-
 // ----------------------------------------------------------------- Arrow format strings (table.hip)
 dfgpu_field parse_format(const char* fmt, bool nullable);
 std::string format_of(const dfgpu_field& f);

@@ -3,11 +3,15 @@
 // The fused FilterExec + ProjectionExec + AggregateExec node interprets its expression forest per row
 // (rowprog.hpp).  Measured on MI355X (profiles/r1_q1_pmc.md) the interpreter is bound by per-instruction
 // latency — operand fetch, scalar loads of the instruction words, dispatch branches — at about 12 % of HBM
-// peak for TPC-H Q1.  For large inputs the node is therefore specialised at plan time: the hand-written HIP
-// kernel skeleton (aggregate.hip, `agg_node_source`) gets the forest spliced in as straight-line typed code
-// (RowProgramCompiler::finish emits it), is compiled once with hiprtc for gfx950, cached on disk as a code object and
-// per process by its source text, and loaded as a module once per device.  Small inputs (and any forest hiprtc
-// rejects) keep using the interpreter.
+// peak for TPC-H Q1.  For large inputs the node is therefore specialised at plan time: a hand-written HIP kernel
+// skeleton gets the forest spliced in as straight-line typed code, is compiled once with hiprtc for gfx950, cached
+// on disk as a code object and per process by its source text, and loaded as a module once per device.  Small
+// inputs (and any forest hiprtc rejects) keep using the interpreter.  aggregate.hip has three such skeletons:
+//   agg_node_source       small-domain keys: LDS cells per key                 (kernel agg_node)
+//   agg_dense_node_source one dense integer key: groups numbered by rank       (dense_minmax, dense_setbits, dense_accumulate)
+//   agg_runs_node_source  input ordered by its key: one run = one group        (runs_accumulate)
+// The forest's code comes from RowProgramCompiler::finish (rowprog.hip), which also owns the text it needs in front
+// of it (rowprog_source_prelude): every skeleton starts with that prelude.
 #include <hip/hiprtc.h>
 
 #include <sys/stat.h>

@@ -617,4 +617,31 @@ bool RowProgramCompiler::finish(CompiledProgram& cp, std::string& why) {
   return true;
 }
 
+// What the source emitted above needs in front of it: `src_loads`, `src_pred` and `src_outs` of a CompiledProgram compile only
+// after this text, inside a kernel whose parameter is called `a` and begins with `col[RP_MAX_COLS]` and `valid[RP_MAX_COLS]`
+// (the slots of RowProgram::col_data / col_valid), with the row index in `i`.  A name the emitter starts to use is defined HERE.
+const char* rowprog_source_prelude() {
+  return R"SRC(
+typedef __int128 i128;
+typedef unsigned __int128 u128;
+typedef unsigned long long U64;
+typedef long long I64;
+typedef unsigned int U32;
+typedef int I32;
+typedef unsigned char U8;
+#define BLOCK 256
+__device__ __forceinline__ double v2f(i128 x) { return __longlong_as_double((long long)(U64)x); }
+__device__ __forceinline__ i128 f2v(double d) { return (i128)(u128)(U64)__double_as_longlong(d); }
+__device__ __forceinline__ long long f64ord(U64 bits) { long long b = (long long)bits; return b ^ (long long)((U64)(b >> 63) >> 1); }
+__device__ __forceinline__ I32 date32_part(I32 days, int part) {  // device.hpp date32_part
+  const I64 z = (I64)days + 719468, era = (z >= 0 ? z : z - 146096) / 146097, doe = z - era * 146097;
+  const I64 yoe = (doe - doe / 1460 + doe / 36524 - doe / 146096) / 365, doy = doe - (365 * yoe + yoe / 4 - yoe / 100), mp = (5 * doy + 2) / 153;
+  const I64 d = doy - (153 * mp + 2) / 5 + 1, m = mp < 10 ? mp + 3 : mp - 9, y = yoe + era * 400 + (m <= 2 ? 1 : 0);
+  return (I32)(part == 0 ? y : part == 1 ? m : d);
+}
+__device__ __forceinline__ bool kt(i128 v, bool n) { return !n && ((int)v & 1); }
+__device__ __forceinline__ bool kf(i128 v, bool n) { return !n && !((int)v & 1); }
+)SRC";
+}
+
 }  // namespace dfgpu

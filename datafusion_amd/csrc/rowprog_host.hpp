@@ -34,7 +34,8 @@ struct CompiledProgram {
   int tile_pred = -1;          // operand byte of the predicate, -1 = none
   std::vector<int> tile_outs;  // operand byte per output
   // the same forest as HIP source for runtime-specialised kernels (jit.hip): statements over `i` (row) and
-  // `a.col[s]` / `a.valid[s]` defining, per value v, `const i128 V<v>` and `const bool N<v>` (NULL flag)
+  // `a.col[s]` / `a.valid[s]` defining, per value v, `const i128 V<v>` and `const bool N<v>` (NULL flag);
+  // they compile after rowprog_source_prelude()
   std::string src_loads;       // column loads + widening
   std::string src_pred;        // predicate segment
   std::string src_outs;        // output segment
@@ -92,5 +93,8 @@ class RowProgramCompiler {
     failed_ = true;
   }
 };
+
+// the text every generated source opens with: the names the source emitted by RowProgramCompiler::finish uses (rowprog.hip)
+const char* rowprog_source_prelude();
 
 }  // namespace dfgpu
