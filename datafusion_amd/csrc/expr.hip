@@ -178,7 +178,7 @@ __global__ __launch_bounds__(BLOCK) void k_divmod(int is_mod, Operand<T> a, Oper
       const bool ovf = ox || oy;
       if (ovf) bad |= 2u;
       else if (y == 0) bad |= 1u;
-      else if (y == (T)-1 && x == (T)((T)1 << (sizeof(T) * 8 - 1))) bad |= 2u;
+      else if (y == (T)-1 && x == (T)((T)1 << (sizeof(T) * 8 - 1))) bad |= is_mod ? 0u : 2u;   // MIN % -1 = 0 (rem: mod_wrapping), MIN / -1 overflows
       else v = is_mod ? (T)(x % y) : (T)(x / y);
     }
     out[i] = v;
@@ -497,8 +497,10 @@ static Datum eval_divmod(int op, const Datum& a, const Datum& b, int64_t nrows) 
     unsigned flags = (ox || oy) ? 2u : 0u;
     if (!flags && y == 0) flags = 1u;
     const i128 lowest = out_field.type == DFGPU_INT32 ? (i128)INT32_MIN : out_field.type == DFGPU_INT64 ? (i128)INT64_MIN : (i128)((u128)1 << 127);
-    if (!flags && y == -1 && x == lowest) flags = 2u;
+    const bool min_by_minus_one = !flags && y == -1 && x == lowest;
+    if (min_by_minus_one && !is_mod) flags = 2u;
     throw_divmod(flags);
+    if (min_by_minus_one) return make_scalar(out_field, 0, false);   // MIN % -1 = 0 (rem: mod_wrapping)
     return make_scalar(out_field, is_mod ? x % y : x / y, false);
   }
   Datum o;
@@ -590,7 +592,10 @@ static Datum eval_binary(const dfgpu_expr_node& n, const Datum& a, const Datum& 
       std::memcpy(&x, &a.lit_lo, 8);
       std::memcpy(&y, &b.lit_lo, 8);
       if (is_cmp) {
-        bool rr = op == DFGPU_EXPR_EQ ? x == y : op == DFGPU_EXPR_NE ? x != y : op == DFGPU_EXPR_LT ? x < y : op == DFGPU_EXPR_LE ? x <= y : op == DFGPU_EXPR_GT ? x > y : x >= y;
+        // total order, as k_cmp compares the same values in a column (f64_total_key): NaN = NaN, -0.0 < +0.0
+        auto key = [](uint64_t bits) { const int64_t b = (int64_t)bits; return b ^ (int64_t)((uint64_t)(b >> 63) >> 1); };
+        const int64_t kx = key(a.lit_lo), ky = key(b.lit_lo);
+        bool rr = op == DFGPU_EXPR_EQ ? kx == ky : op == DFGPU_EXPR_NE ? kx != ky : op == DFGPU_EXPR_LT ? kx < ky : op == DFGPU_EXPR_LE ? kx <= ky : op == DFGPU_EXPR_GT ? kx > ky : kx >= ky;
         return make_scalar(out_field, rr, isnull);
       }
       double v = op == DFGPU_EXPR_ADD ? x + y : op == DFGPU_EXPR_SUB ? x - y : x * y;

@@ -126,6 +126,10 @@ RpValue RowProgramCompiler::lower_cast(const dfgpu_field& to, RpValue x) {
   const int ft = physical_type(from.type);
   auto unsupported = [&]() -> RpValue { throw Error("cast " + type_name(from) + " -> " + type_name(to) + " is not supported on the GPU path"); };
   if (to.type == DFGPU_DECIMAL128) {
+    if (ft == DFGPU_FLOAT64) {  // rounding + range and precision checks raise errors a row program cannot: column-at-a-time (expr.hip)
+      fail("Float64 -> Decimal128 casts are evaluated column-at-a-time");
+      return literal(to, 0, 0, true);
+    }
     if (!(ft == DFGPU_INT32 || ft == DFGPU_INT64 || ft == DFGPU_UINT8 || ft == DFGPU_DECIMAL128)) return unsupported();
     int fs = from.type == DFGPU_DECIMAL128 ? from.scale : 0;
     if (to.scale < fs) {  // rounding + precision check raise errors a row program cannot: column-at-a-time (expr.hip)
@@ -141,6 +145,10 @@ RpValue RowProgramCompiler::lower_cast(const dfgpu_field& to, RpValue x) {
     return RpValue{x.id, to};  // the widened register already holds the value
   }
   if (to.type == DFGPU_FLOAT64) {
+    if (ft == DFGPU_DECIMAL128) {  // a 128-bit integer to double and a division: column-at-a-time (expr.hip k_cast_div)
+      fail("Decimal128 -> Float64 casts are evaluated column-at-a-time");
+      return literal(to, 0, 0, true);
+    }
     if (!(ft == DFGPU_INT32 || ft == DFGPU_INT64)) return unsupported();
     return RpValue{emit(RP_I2F, x.id, x.id, 0), to};
   }
@@ -630,6 +638,8 @@ typedef unsigned int U32;
 typedef int I32;
 typedef unsigned char U8;
 #define BLOCK 256
+// every Float64 node rounds once, as BinaryExpr evaluates it: `a * b + c` must not become one fused multiply-add
+#pragma clang fp contract(off)
 __device__ __forceinline__ double v2f(i128 x) { return __longlong_as_double((long long)(U64)x); }
 __device__ __forceinline__ i128 f2v(double d) { return (i128)(u128)(U64)__double_as_longlong(d); }
 __device__ __forceinline__ long long f64ord(U64 bits) { long long b = (long long)bits; return b ^ (long long)((U64)(b >> 63) >> 1); }

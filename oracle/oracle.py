@@ -405,9 +405,22 @@ def evaluate(expr, table: pa.Table) -> Datum:
         src, dst = orc_type(d.typ), orc_type(to)
         m = d.values.shape[0]
         if dst == ORC_I128 and src == ORC_F64:   # arrow-cast cast_floating_point_to_decimal128: (v * 10^scale).round() as i128
-            mv = d.values.astype(np.float64) * float(10 ** to.scale)
-            r = np.where(np.abs(mv) < 2.0 ** 52, np.copysign(np.floor(np.abs(mv) + 0.5), mv), mv)
-            return Datum(_i128_np([int(x) for x in r.tolist()]), to, d.valid, d.scalar)
+            # f64::round is half away from zero of the double product itself.  floor(|x| + 0.5) is not: 0.49999999999999994 + 0.5 rounds
+            # up to 1.0.  x - trunc(x) is exact, so comparing it with 0.5 is.  The cast is not `safe`: a valid row whose product is not
+            # finite or leaves the i128 range, or whose result needs more than the target precision, is an error
+            with np.errstate(all="ignore"):
+                mv = d.values.astype(np.float64) * float(10 ** to.scale)
+                t = np.trunc(mv)
+                r = t + np.where(np.abs(mv - t) >= 0.5, np.copysign(1.0, mv), 0.0)
+            live = np.ones(m, bool) if d.valid is None else d.valid
+            fits = (r >= -2.0 ** 127) & (r < 2.0 ** 127)     # False for NaN
+            if (live & ~fits).any():
+                raise OverflowError(f"Arrow error: Cast error: Cannot cast to {to}. Overflowing on {d.values[np.flatnonzero(live & ~fits)[0]]}")
+            out = [int(x) if ok else 0 for x, ok in zip(r.tolist(), (live & fits).tolist())]
+            for v in out:
+                if abs(v) >= 10 ** to.precision:
+                    raise OverflowError(f"Arrow error: Invalid argument error: {v} is too large to store in a {to}")
+            return Datum(_i128_np(out), to, d.valid, d.scalar)
         if dst == ORC_I128:
             out = np.zeros((m, 2), np.uint64)
             L.orc_cast_to_i128(src, C.c_void_p(np.ascontiguousarray(d.values).ctypes.data), C.c_int64(m), C.c_void_p(out.ctypes.data))
