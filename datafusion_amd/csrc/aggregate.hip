@@ -41,9 +41,13 @@ constexpr int MAX_AGGS = 16;
 constexpr uint32_t PROBE_LIMIT = 256;  // longer probe sequence => table too full => regrow
 
 // accumulator kinds
-enum AccKind : int { ACC_SUM_I64 = 0, ACC_SUM_I128 = 1, ACC_SUM_F64 = 2, ACC_MIN_I64 = 3, ACC_MAX_I64 = 4, ACC_COUNT = 5, ACC_COUNT_STAR = 6 };
-// how a value is loaded & widened
-enum ValKind : int { VAL_I32 = 0, VAL_I64 = 1, VAL_I128 = 2, VAL_F64 = 3, VAL_U8 = 4, VAL_F64_ORDERED = 5, VAL_I32_TO_F64 = 6, VAL_I64_TO_F64 = 7, VAL_U32 = 8, VAL_U64 = 9 };
+// (ACC_AND / ACC_OR / ACC_XOR: bit_and / bit_or / bit_xor over the 64-bit cell, bool_and / bool_or over a 0/1 cell — exact, associative
+// and commutative like the integer sums, so every site folds and merges them with the operation itself)
+enum AccKind : int { ACC_SUM_I64 = 0, ACC_SUM_I128 = 1, ACC_SUM_F64 = 2, ACC_MIN_I64 = 3, ACC_MAX_I64 = 4, ACC_COUNT = 5, ACC_COUNT_STAR = 6,
+                     ACC_AND = 7, ACC_OR = 8, ACC_XOR = 9 };
+// how a value is loaded & widened (VAL_BIT: a bit-packed Boolean column, row i = bit i -> 0 / 1)
+enum ValKind : int { VAL_I32 = 0, VAL_I64 = 1, VAL_I128 = 2, VAL_F64 = 3, VAL_U8 = 4, VAL_F64_ORDERED = 5, VAL_I32_TO_F64 = 6, VAL_I64_TO_F64 = 7, VAL_U32 = 8, VAL_U64 = 9,
+                     VAL_BIT = 10 };
 
 struct AccDesc {
   const void* values;          // input value column (null for COUNT(*))
@@ -89,6 +93,7 @@ __device__ __forceinline__ void load_value(const AccDesc& d, int64_t i, uint64_t
     case VAL_F64_ORDERED: lo = (uint64_t)f64_ordered(((const double*)d.values)[i]); break;
     case VAL_I32_TO_F64: lo = (uint64_t)__double_as_longlong((double)((const int32_t*)d.values)[i]); break;
     case VAL_I64_TO_F64: lo = (uint64_t)__double_as_longlong((double)((const int64_t*)d.values)[i]); break;
+    case VAL_BIT: lo = (((const uint64_t*)d.values)[i >> 6] >> (i & 63)) & 1ull; break;
   }
 }
 
@@ -118,6 +123,10 @@ __device__ __forceinline__ void load_values_batch(int val, const void* values, c
     case VAL_U8:
 #pragma unroll
       for (int u = 0; u < U; u++) lo[u] = (live >> u) & 1u ? ((const uint8_t*)values)[ii[u]] : 0u;
+      break;
+    case VAL_BIT:   // (rows where they lie only: a bit-packed column is never moved — partitioned_accumulate)
+#pragma unroll
+      for (int u = 0; u < U; u++) lo[u] = (live >> u) & 1u ? (((const uint64_t*)values)[ii[u] >> 6] >> (ii[u] & 63)) & 1ull : 0ull;
       break;
     case VAL_I128: {
       ulonglong2 v[U];
@@ -169,13 +178,32 @@ __device__ __forceinline__ void accumulate_cell(int kind, unsigned long long* lo
     case ACC_SUM_F64: atomicAdd(reinterpret_cast<double*>(lo_cell), __longlong_as_double((long long)lo)); break;
     case ACC_MIN_I64: atomicMin(reinterpret_cast<long long*>(lo_cell), (long long)lo); break;
     case ACC_MAX_I64: atomicMax(reinterpret_cast<long long*>(lo_cell), (long long)lo); break;
-    default: atomicAdd(lo_cell, 1ull); break;  // COUNT / COUNT(*)
+    case ACC_AND: atomicAnd(lo_cell, (unsigned long long)lo); break;
+    case ACC_OR: atomicOr(lo_cell, (unsigned long long)lo); break;
+    case ACC_XOR: atomicXor(lo_cell, (unsigned long long)lo); break;
+    case ACC_COUNT:
+    case ACC_COUNT_STAR: atomicAdd(lo_cell, 1ull); break;
+    default: break;  // (no other kind: plan_for makes them all)
   }
 }
 __host__ __device__ __forceinline__ unsigned long long acc_identity(int kind) {
   if (kind == ACC_MIN_I64) return (unsigned long long)INT64_MAX;
   if (kind == ACC_MAX_I64) return (unsigned long long)INT64_MIN;
+  if (kind == ACC_AND) return ~0ull;
   return 0ull;
+}
+// two totals of one 64-bit accumulator into one (replica folds, merges of per-workgroup and per-batch totals); counts are totals by now
+// and add.  ACC_SUM_I128 is folded by its callers (two words and a carry).
+__device__ __forceinline__ unsigned long long acc_fold64(int kind, unsigned long long a, unsigned long long v) {
+  switch (kind) {
+    case ACC_SUM_F64: return (unsigned long long)__double_as_longlong(__longlong_as_double((long long)a) + __longlong_as_double((long long)v));
+    case ACC_MIN_I64: return (unsigned long long)min((long long)a, (long long)v);
+    case ACC_MAX_I64: return (unsigned long long)max((long long)a, (long long)v);
+    case ACC_AND: return a & v;
+    case ACC_OR: return a | v;
+    case ACC_XOR: return a ^ v;
+    default: return a + v;  // ACC_SUM_I64, ACC_COUNT, ACC_COUNT_STAR
+  }
 }
 
 // ------------------------------------------------------------------------------ intern
@@ -680,7 +708,7 @@ __global__ __launch_bounds__(BLOCK) void k_fill_u64(unsigned long long v, int64_
 }
 
 // -------------------------------------------------------------------------------- emit
-// mode: 0 copy i64 (lo), 1 i128 (lo,hi), 2 ordered-i64 -> f64, 3 i64 -> i32 narrowing, 4 i64 -> u8
+// mode: 0 copy i64 (lo), 1 i128 (lo,hi), 2 ordered-i64 -> f64, 3 i64 -> i32 narrowing, 4 i64 -> u8 (k_emit_set adds 5: values in place, 6: bit-packed Boolean)
 __global__ __launch_bounds__(BLOCK) void k_emit_values(int mode, const unsigned long long* lo, const unsigned long long* hi, const uint32_t* seen,
                                                        int64_t n, void* out, uint8_t* valid_bytes) {
   for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
@@ -747,6 +775,7 @@ __global__ __launch_bounds__(BLOCK) void k_emit_set(EmitSet s, int64_t n, unsign
   const int64_t wv = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * BLOCK) >> 6;
   const bool avg = e.kind == 1, var = e.kind == 2, counted = avg || var;
   const bool need_lo = avg || (!var && e.mode != 5), need_hi = var || (avg ? e.mode != 0 : e.mode == 1);
+  const bool bool_out = !counted && e.mode == 6;
   unsigned long long valid_rows = 0;
   bool overflow = false;
   for (int64_t w0 = wv * U; w0 < n_words; w0 += n_waves * U) {
@@ -773,7 +802,7 @@ __global__ __launch_bounds__(BLOCK) void k_emit_set(EmitSet s, int64_t n, unsign
 #pragma unroll
     for (int u = 0; u < U; u++) {
       const int64_t i = ((w0 + u) << 6) + lane;
-      bool ok = false;
+      bool ok = false, bit = false;
       if (in[u]) {
         if (var) {
           // variance.rs evaluate: m2 / (n - 1) or m2 / n; NULL below two (sample) or one (population) values
@@ -790,6 +819,7 @@ __global__ __launch_bounds__(BLOCK) void k_emit_set(EmitSet s, int64_t n, unsign
             case 2: ((double*)e.dst)[i] = ok ? f64_from_ordered((int64_t)lo[u]) : 0.0; break;
             case 3: ((int32_t*)e.dst)[i] = ok ? (int32_t)(int64_t)lo[u] : 0; break;
             case 4: ((uint8_t*)e.dst)[i] = ok ? (uint8_t)lo[u] : 0; break;
+            case 6: bit = ok && (lo[u] & 1ull); break;   // a Boolean result: the word of 64 groups is stored below
             default: break;   // 5: the values are in place already (the runs node's interleaved cells), only the validity is made
           }
         } else {
@@ -808,6 +838,10 @@ __global__ __launch_bounds__(BLOCK) void k_emit_set(EmitSet s, int64_t n, unsign
             ((double*)e.dst)[i] = ok ? __longlong_as_double((long long)lo[u]) / (double)c : 0.0;
           }
         }
+      }
+      if (bool_out) {   // bit-packed values: a whole word per 64 groups, like the validity word
+        const uint64_t bits = ballot64(bit);
+        if (lane == 0 && w0 + u < n_words) ((uint64_t*)e.dst)[w0 + u] = bits;
       }
       const uint64_t word = ballot64(ok);
       if (e.valid_words && lane == 0 && w0 + u < n_words) e.valid_words[w0 + u] = word;
@@ -1158,9 +1192,31 @@ static AccPlan plan_for(int func, const dfgpu_field& t, bool merging_counts) {
       }
       break;
     }
+    case DFGPU_AGG_BIT_AND:
+    case DFGPU_AGG_BIT_OR:
+    case DFGPU_AGG_BIT_XOR: {
+      // bit_and_or_xor.rs: the integer types, the result is the argument's type.  The cell is 64 bits wide and the value arrives sign-
+      // extended (Int32) or zero-extended (UInt8 / UInt32): AND, OR and XOR act on every bit position by itself, so the low bits the
+      // emit keeps (k_emit_set modes 3 / 4) are exactly the narrow type's result whatever the extension put above them
+      const int k = func == DFGPU_AGG_BIT_AND ? ACC_AND : func == DFGPU_AGG_BIT_OR ? ACC_OR : ACC_XOR;
+      switch (t.type) {
+        case DFGPU_INT32: return {k, VAL_I32, false};
+        case DFGPU_INT64: return {k, VAL_I64, false};
+        case DFGPU_UINT8: return {k, VAL_U8, false};
+        case DFGPU_UINT32: return {k, VAL_U32, false};
+        case DFGPU_UINT64: return {k, VAL_U64, false};
+      }
+      throw Error(std::string(func == DFGPU_AGG_BIT_AND ? "BIT_AND" : func == DFGPU_AGG_BIT_OR ? "BIT_OR" : "BIT_XOR") + " over " + type_name(t) + " is not supported on the GPU path");
+    }
+    case DFGPU_AGG_BOOL_AND:
+    case DFGPU_AGG_BOOL_OR:
+      // bool_and_or.rs: AND / OR over a 0/1 cell; a column is read bit by bit (VAL_BIT), a row program's Boolean output is a 0/1 register
+      if (t.type == DFGPU_BOOL) return {func == DFGPU_AGG_BOOL_AND ? ACC_AND : ACC_OR, VAL_BIT, false};
+      throw Error(std::string(func == DFGPU_AGG_BOOL_AND ? "BOOL_AND" : "BOOL_OR") + " over " + type_name(t) + " is not supported on the GPU path");
   }
   throw Error("aggregate over " + type_name(t) + " is not supported on the GPU path");
 }
+static bool is_bitwise(int func) { return func >= DFGPU_AGG_BIT_AND && func <= DFGPU_AGG_BOOL_OR; }
 
 // MIN / MAX over Decimal128 wider than 18 digits: is every (valid) value representable in 64 bits?
 static bool wide_minmax(int func, const dfgpu_field& t) {
@@ -1312,13 +1368,8 @@ __global__ __launch_bounds__(BLOCK) void k_agg_fused(RowProgram p, int n_prologu
         if (!s_seen[cell]) continue;
         any = true;
         const unsigned long long vlo = s_lo[cell], vhi = s_hi[cell];
-        switch (kind) {
-          case ACC_SUM_I128: { unsigned long long o = lo; lo += vlo; hi += vhi + (lo < o ? 1ull : 0ull); break; }
-          case ACC_SUM_F64: lo = (unsigned long long)__double_as_longlong(__longlong_as_double((long long)lo) + __longlong_as_double((long long)vlo)); break;
-          case ACC_MIN_I64: lo = (unsigned long long)min((long long)lo, (long long)vlo); break;
-          case ACC_MAX_I64: lo = (unsigned long long)max((long long)lo, (long long)vlo); break;
-          default: lo += vlo; break;  // SUM_I64 / COUNT / COUNT(*)
-        }
+        if (kind == ACC_SUM_I128) { unsigned long long o = lo; lo += vlo; hi += vhi + (lo < o ? 1ull : 0ull); }
+        else lo = acc_fold64(kind, lo, vlo);
       }
       if (!any) continue;
       if (kind == ACC_COUNT || kind == ACC_COUNT_STAR) kind = ACC_SUM_I64;  // merge counts by adding
@@ -1447,7 +1498,12 @@ __global__ __launch_bounds__(BLOCK) void k_agg_fused_tile(TileProgram p, int pre
           case ACC_SUM_F64: atomicAdd(reinterpret_cast<double*>(c), __longlong_as_double((long long)lo)); break;
           case ACC_MIN_I64: atomicMin(reinterpret_cast<long long*>(c), (long long)lo); break;
           case ACC_MAX_I64: atomicMax(reinterpret_cast<long long*>(c), (long long)lo); break;
-          default: atomicAdd(c, 1ull); break;  // COUNT / COUNT(*)
+          case ACC_AND: atomicAnd(c, (unsigned long long)lo); break;
+          case ACC_OR: atomicOr(c, (unsigned long long)lo); break;
+          case ACC_XOR: atomicXor(c, (unsigned long long)lo); break;
+          case ACC_COUNT:
+          case ACC_COUNT_STAR: atomicAdd(c, 1ull); break;
+          default: break;
         }
       }
       if (seen & ~s_seen[base]) atomicOr(&s_seen[base], seen);
@@ -1494,15 +1550,7 @@ __global__ __launch_bounds__(BLOCK) void k_agg_fused_tile(TileProgram p, int pre
       lo = (unsigned long long)v;
       hi = (unsigned long long)(v >> 64);
     } else {
-      for (int q = 0; q < nrep; q++) {
-        const unsigned long long v = c[q];
-        switch (kind) {
-          case ACC_SUM_F64: lo = (unsigned long long)__double_as_longlong(__longlong_as_double((long long)lo) + __longlong_as_double((long long)v)); break;
-          case ACC_MIN_I64: lo = (unsigned long long)min((long long)lo, (long long)v); break;
-          case ACC_MAX_I64: lo = (unsigned long long)max((long long)lo, (long long)v); break;
-          default: lo += v; break;  // SUM_I64 / COUNT / COUNT(*)
-        }
-      }
+      for (int q = 0; q < nrep; q++) lo = acc_fold64(kind, lo, c[q]);
       if (kind == ACC_COUNT || kind == ACC_COUNT_STAR) kind = ACC_SUM_I64;  // merge counts by adding
     }
     accumulate_cell(kind, d.tmp_lo + key, d.tmp_hi ? d.tmp_hi + key : nullptr, lo, hi);
@@ -2032,9 +2080,9 @@ struct Args {
   long long begin, end;
   int L, nrep;
 };
-enum { SUM_I64 = 0, SUM_I128 = 1, SUM_F64 = 2, MIN_I64 = 3, MAX_I64 = 4, COUNT = 5, COUNT_STAR = 6 };
+enum { SUM_I64 = 0, SUM_I128 = 1, SUM_F64 = 2, MIN_I64 = 3, MAX_I64 = 4, COUNT = 5, COUNT_STAR = 6, AND_U64 = 7, OR_U64 = 8, XOR_U64 = 9 };
 __device__ __forceinline__ U64 identity_of(int kind) {
-  return kind == MIN_I64 ? 0x7fffffffffffffffull : kind == MAX_I64 ? 0x8000000000000000ull : 0ull;
+  return kind == MIN_I64 ? 0x7fffffffffffffffull : kind == MAX_I64 ? 0x8000000000000000ull : kind == AND_U64 ? ~0ull : 0ull;
 }
 __device__ __forceinline__ int local_slot(unsigned int* s_key, int L, unsigned int key) {
   const unsigned int want = key + 1u;
@@ -2061,10 +2109,16 @@ __device__ __forceinline__ void global_accumulate(int kind, U64* lo_cell, U64* h
     case SUM_F64: atomicAdd(reinterpret_cast<double*>(lo_cell), __longlong_as_double((long long)lo)); break;
     case MIN_I64: atomicMin(reinterpret_cast<long long*>(lo_cell), (long long)lo); break;
     case MAX_I64: atomicMax(reinterpret_cast<long long*>(lo_cell), (long long)lo); break;
-    default: atomicAdd(lo_cell, 1ull); break;
+    case AND_U64: atomicAnd(lo_cell, lo); break;
+    case OR_U64: atomicOr(lo_cell, lo); break;
+    case XOR_U64: atomicXor(lo_cell, lo); break;
+    case COUNT:
+    case COUNT_STAR: atomicAdd(lo_cell, 1ull); break;
+    default: break;
   }
 }
 )SRC";
+  static_assert(ACC_AND == 7 && ACC_OR == 8 && ACC_XOR == 9 && ACC_COUNT == 5 && ACC_COUNT_STAR == 6, "the enum of the generated source repeats AccKind");
   src += "#define NACC " + S(accs.n) + "\n#define NCELL " + S(accs.ncell) + "\n";
   src += "__device__ __forceinline__ int acc_kind(int k) { switch (k) {";
   for (int k = 0; k < accs.n; k++) src += " case " + S(k) + ": return " + S(accs.a[k].kind) + ";";
@@ -2127,7 +2181,12 @@ extern "C" __global__ __launch_bounds__(BLOCK) void agg_node(Args a) {
       case ACC_SUM_F64: src += "atomicAdd(reinterpret_cast<double*>" + c + ", __longlong_as_double((long long)" + vlo + "));"; break;
       case ACC_MIN_I64: src += "atomicMin(reinterpret_cast<long long*>" + c + ", (long long)" + vlo + ");"; break;
       case ACC_MAX_I64: src += "atomicMax(reinterpret_cast<long long*>" + c + ", (long long)" + vlo + ");"; break;
-      default: src += "atomicAdd(" + c + ", 1ull);"; break;
+      case ACC_AND: src += "atomicAnd(" + c + ", " + vlo + ");"; break;
+      case ACC_OR: src += "atomicOr(" + c + ", " + vlo + ");"; break;
+      case ACC_XOR: src += "atomicXor(" + c + ", " + vlo + ");"; break;
+      case ACC_COUNT:
+      case ACC_COUNT_STAR: src += "atomicAdd(" + c + ", 1ull);"; break;
+      default: throw Error("small-domain node: accumulator kind " + S(accs.a[k].kind) + " has no generated form");
     }
     src += " }\n";
   }
@@ -2167,7 +2226,10 @@ extern "C" __global__ __launch_bounds__(BLOCK) void agg_node(Args a) {
           case SUM_F64: lo = (U64)__double_as_longlong(__longlong_as_double((long long)lo) + __longlong_as_double((long long)v)); break;
           case MIN_I64: lo = (U64)min((long long)lo, (long long)v); break;
           case MAX_I64: lo = (U64)max((long long)lo, (long long)v); break;
-          default: lo += v; break;
+          case AND_U64: lo &= v; break;
+          case OR_U64: lo |= v; break;
+          case XOR_U64: lo ^= v; break;
+          default: lo += v; break;  // SUM_I64 / COUNT / COUNT_STAR
         }
       }
       if (kind == COUNT || kind == COUNT_STAR) kind = SUM_I64;
@@ -2249,6 +2311,38 @@ __device__ __forceinline__ long long seg_max_i64(long long v, bool head) {
   return v;
 }
 )SRC";
+// The bitwise twins of seg_min_i64 / seg_max_i64, and of the runs node's all_min_i64 / all_max_i64.  A generated source carries them only
+// when one of its accumulators is ACC_AND / ACC_OR / ACC_XOR (is_bitwise_kind): the source of every other node stays, character for
+// character, what it was before these kinds existed, and so does its code object.  (seg_or_u64 is also what dense_setbits merges its
+// bitmap words with: the dense node's source has it always, at its old place.)
+static const char* const SEG_OR_SOURCE = R"SRC(__device__ __forceinline__ U64 seg_or_u64(U64 v, bool head) {
+  SEG_SCAN(const U64 o = __shfl_up(v, d, 64); if (lane >= d && !f) v |= o;)
+  return v;
+}
+)SRC";
+static const char* const SEG_AND_XOR_SOURCE = R"SRC(__device__ __forceinline__ U64 seg_and_u64(U64 v, bool head) {
+  SEG_SCAN(const U64 o = __shfl_up(v, d, 64); if (lane >= d && !f) v &= o;)
+  return v;
+}
+__device__ __forceinline__ U64 seg_xor_u64(U64 v, bool head) {
+  SEG_SCAN(const U64 o = __shfl_up(v, d, 64); if (lane >= d && !f) v ^= o;)
+  return v;
+}
+)SRC";
+static const char* const ALL_BITWISE_SOURCE = R"SRC(__device__ __forceinline__ U64 all_and_u64(U64 v) {
+  _Pragma("unroll") for (int d = 32; d >= 1; d >>= 1) v &= __shfl_xor(v, d, 64);
+  return v;
+}
+__device__ __forceinline__ U64 all_or_u64(U64 v) {
+  _Pragma("unroll") for (int d = 32; d >= 1; d >>= 1) v |= __shfl_xor(v, d, 64);
+  return v;
+}
+__device__ __forceinline__ U64 all_xor_u64(U64 v) {
+  _Pragma("unroll") for (int d = 32; d >= 1; d >>= 1) v ^= __shfl_xor(v, d, 64);
+  return v;
+}
+)SRC";
+static bool is_bitwise_kind(int kind) { return kind == ACC_AND || kind == ACC_OR || kind == ACC_XOR; }
 
 static std::string agg_dense_node_source(const CompiledProgram& cp, int key_val, const std::vector<DenseAcc>& accs) {
   auto S = [](long long v) { return std::to_string(v); };
@@ -2277,6 +2371,7 @@ struct Args {
 };
 )SRC";
   src += SEG_SCAN_SOURCE;
+  if (std::any_of(accs.begin(), accs.end(), [](const DenseAcc& c) { return is_bitwise_kind(c.kind); })) src += SEG_AND_XOR_SOURCE;
   src += R"SRC(
 extern "C" __global__ __launch_bounds__(BLOCK) void dense_minmax(Args a) {
   long long mn = 0x7fffffffffffffffll, mx = -0x7fffffffffffffffll - 1;
@@ -2310,11 +2405,9 @@ extern "C" __global__ __launch_bounds__(BLOCK) void dense_minmax(Args a) {
 
 // Adjacent lanes that target the same bitmap word are merged (segmented OR) into ONE atomic per word and wave;
 // bits only ever go 0 -> 1, so the plain (possibly stale) read is a safe filter: it can only cause a redundant atomic.
-__device__ __forceinline__ U64 seg_or_u64(U64 v, bool head) {
-  SEG_SCAN(const U64 o = __shfl_up(v, d, 64); if (lane >= d && !f) v |= o;)
-  return v;
-}
-extern "C" __global__ __launch_bounds__(BLOCK) void dense_setbits(Args a) {
+)SRC";
+  src += SEG_OR_SOURCE;
+  src += R"SRC(extern "C" __global__ __launch_bounds__(BLOCK) void dense_setbits(Args a) {
   const long long stride = (long long)gridDim.x * BLOCK;
   const long long n_round = a.begin + (a.end - a.begin + BLOCK - 1) / BLOCK * BLOCK;
   for (long long i = a.begin + (long long)blockIdx.x * BLOCK + threadIdx.x; i < n_round; i += stride) {
@@ -2404,9 +2497,20 @@ extern "C" __global__ __launch_bounds__(BLOCK) void dense_accumulate(Args a) {
         src += "      const long long t = seg_max_i64(" + X + "ok ? (long long)" + X + "lo : (-0x7fffffffffffffffll - 1), head);\n      if (tail && cnt) { seen |= " +
                S(1ll << k) + "u; atomicMax(reinterpret_cast<long long*>" + cell + ", t); }\n";
         break;
-      default:
+      case ACC_AND:
+        src += "      const U64 t = seg_and_u64(" + X + "ok ? " + X + "lo : ~0ull, head);\n      if (tail && cnt) { seen |= " + S(1ll << k) + "u; atomicAnd(" + cell + ", t); }\n";
+        break;
+      case ACC_OR:
+        src += "      const U64 t = seg_or_u64(" + X + "ok ? " + X + "lo : 0ull, head);\n      if (tail && cnt) { seen |= " + S(1ll << k) + "u; atomicOr(" + cell + ", t); }\n";
+        break;
+      case ACC_XOR:
+        src += "      const U64 t = seg_xor_u64(" + X + "ok ? " + X + "lo : 0ull, head);\n      if (tail && cnt) { seen |= " + S(1ll << k) + "u; atomicXor(" + cell + ", t); }\n";
+        break;
+      case ACC_COUNT:
+      case ACC_COUNT_STAR:
         src += "      if (tail && cnt) { seen |= " + S(1ll << k) + "u; atomicAdd(" + cell + ", cnt); }\n";
         break;
+      default: throw Error("dense-key node: accumulator kind " + S(c.kind) + " has no generated form");
     }
     src += "    }\n";
   }
@@ -2751,7 +2855,10 @@ __global__ __launch_bounds__(PART_BLOCK) void k_dense_accumulate_parts(const Par
         case ACC_SUM_F64: atomicAdd(reinterpret_cast<double*>(c), __longlong_as_double((long long)v)); break;
         case ACC_MIN_I64: atomicMin(reinterpret_cast<long long*>(c), (long long)v); break;
         case ACC_MAX_I64: atomicMax(reinterpret_cast<long long*>(c), (long long)v); break;
-        default: atomicAdd(c, v); break;
+        case ACC_AND: atomicAnd(c, v); break;
+        case ACC_OR: atomicOr(c, v); break;
+        case ACC_XOR: atomicXor(c, v); break;
+        default: atomicAdd(c, v); break;   // ACC_SUM_I64 and the counts' totals
       }
     }
   }
@@ -2810,7 +2917,7 @@ struct PartValues {     // what the partitioned accumulation leaves: totals and 
 static int part_val_width(int val) {
   switch (val) {
     case VAL_I32: case VAL_U32: case VAL_I32_TO_F64: return 4;
-    case VAL_U8: return 1;
+    case VAL_U8: case VAL_BIT: return 1;   // (VAL_BIT: never moved — partitioned_accumulate; counted as a byte a row where it is read in place)
     case VAL_I128: return 16;
     default: return 8;
   }
@@ -2854,6 +2961,9 @@ static bool partitioned_accumulate(const void* key, int kt, int64_t n_in, long l
   // — range x workgroups of them, against the 2 x (key + arguments) bytes per row the move costs
   const bool in_place = partitioned_in_place(range, all);
   if (key_map && !in_place) return false;   // (a mapped key cannot be moved by range: the caller maps it first)
+  if (!in_place)   // a bit-packed Boolean argument (bool_and / bool_or) has no bytes of its own to move with its row: the row-at-a-time kernels
+    for (const PartAcc& a : all)
+      if (a.data && a.val == VAL_BIT) return false;
   if (in_place) {
     wshift = 6;
     while (((range - 1) >> wshift) >= 1) wshift++;
@@ -3117,7 +3227,7 @@ static bool dense_accumulate_partitioned(const Aggregate& A, const Table& in, co
     auto narrow = [&](const Column& v) { return acc_val[u] != VAL_I128 || (v.field.type == DFGPU_DECIMAL128 && v.field.precision <= 18) ? 1 : 0; };
     if (c >= 0 && c < (int)in.cols.size()) {
       const Column& col = in.cols[(size_t)c];
-      if (col.validity || col.dict) return false;
+      if (col.validity || col.dict || col.field.type == DFGPU_BOOL) return false;   // (bit-packed: not moved — dense_accumulate takes it)
       all[u].data = col.ptr();
       all[u].narrow = narrow(col);
       continue;
@@ -3192,10 +3302,7 @@ __global__ __launch_bounds__(BLOCK) void k_merge_group_totals(const uint32_t* __
           a.acc_hi[g] += hi + ((old + v) < old ? 1ull : 0ull);
           break;
         }
-        case ACC_SUM_F64: a.acc_lo[g] = (unsigned long long)__double_as_longlong(__longlong_as_double((long long)a.acc_lo[g]) + __longlong_as_double((long long)v)); break;
-        case ACC_MIN_I64: if ((long long)v < (long long)a.acc_lo[g]) a.acc_lo[g] = v; break;
-        case ACC_MAX_I64: if ((long long)v > (long long)a.acc_lo[g]) a.acc_lo[g] = v; break;
-        default: a.acc_lo[g] += v; break;   // SUM_I64 and the counts
+        default: a.acc_lo[g] = acc_fold64(a.kind, a.acc_lo[g], v); break;   // (AND / OR / XOR fold like the sums and the counts: with the operation)
       }
       if (a.seen) a.seen[g] = 1u;
     }
@@ -3217,6 +3324,10 @@ static bool general_accumulate_partitioned(const InternCtx& ictx, const uint32_t
   // cheap refusals first (the row -> group pass below is a random lookup per row)
   const bool off = !option_on("agg.partitioned", true);
   if (off || n < option_int("agg.partitioned_min_rows", 2 * policy().rows_worth_a_pass()) || G1 < 256) return false;
+  // a bit-packed Boolean argument is only read where its rows lie (partitioned_accumulate): declined here, before the row -> group pass
+  if (!partitioned_in_place((uint64_t)G1, all))
+    for (const PartAcc& a : all)
+      if (a.data && a.val == VAL_BIT) return false;
   Runtime& r = rt();
   PartValues pv;
   if (row_slot && (ictx.keyed || ictx.direct) && partitioned_in_place((uint64_t)G1, all)) {
@@ -3744,6 +3855,11 @@ __device__ __forceinline__ long long all_max_i64(long long v) {
   return v;
 }
 )SRC";
+  if (std::any_of(accs.begin(), accs.end(), [](const RunsAcc& c) { return is_bitwise_kind(c.kind); })) {
+    src += SEG_OR_SOURCE;
+    src += SEG_AND_XOR_SOURCE;
+    src += ALL_BITWISE_SOURCE;
+  }
   const int KK = std::max(K, 1);
   src += "#define NACC " + S(KK) + "\n";
   src += "__device__ __forceinline__ void eval_row(const Args& a, const long long i, long long& key, U64 (&Xlo)[NACC], U64 (&Xhi)[NACC], bool (&Xok)[NACC]) {\n";
@@ -3869,10 +3985,23 @@ extern "C" __global__ __launch_bounds__(BLOCK) void runs_accumulate(Args a) {
                "      if (plain) { " + cell + "[g] = (U64)t; " + seen_plain + " }\n"
                "      else if (atom && cnt) { atomicMax(reinterpret_cast<long long*>(" + cell + " + g), t); " + seen_atom + " }\n";
         break;
-      default:  // ACC_COUNT / ACC_COUNT_STAR
+      case ACC_AND:   // (AND and OR have no inverse: no difference of prefixes, a segmented scan like MIN / MAX)
+      case ACC_OR:
+      case ACC_XOR: {
+        const std::string op = c.kind == ACC_AND ? "and" : c.kind == ACC_OR ? "or" : "xor", sym = c.kind == ACC_AND ? "&" : c.kind == ACC_OR ? "|" : "^";
+        const std::string id = c.kind == ACC_AND ? "~0ull" : "0ull", atomic = c.kind == ACC_AND ? "atomicAnd" : c.kind == ACC_OR ? "atomicOr" : "atomicXor";
+        src += "      U64 t = seg_" + op + "_u64(Xok" + ks + " ? Xlo" + ks + " : " + id + ", head);\n"
+               "      if (ext) { const U64 e = all_" + op + "_u64(Eok" + ks + " ? Elo" + ks + " : " + id + "); if (lane_ == 63) t " + sym + "= e; }\n"
+               "      if (plain) { " + cell + "[g] = t; " + seen_plain + " }\n"
+               "      else if (atom && cnt) { " + atomic + "(" + cell + " + g, t); " + seen_atom + " }\n";
+        break;
+      }
+      case ACC_COUNT:
+      case ACC_COUNT_STAR:
         src += "      if (plain) { " + cell + "[g] = cnt; " + seen_plain + " }\n"
                "      else if (atom && cnt) { atomicAdd(" + cell + " + g, cnt); " + seen_atom + " }\n";
         break;
+      default: throw Error("runs node: accumulator kind " + S(c.kind) + " has no generated form");
     }
     src += "    }\n";
   }
@@ -4823,6 +4952,8 @@ static Table agg_emit(Aggregate& A) {
     else if (p.val == VAL_F64_ORDERED) mode = 2;
     else if (vf.type == DFGPU_INT32 || vf.type == DFGPU_DATE32) mode = 3;
     else if (vf.type == DFGPU_UINT8) mode = 4;
+    else if (is_bitwise(a.func) && vf.type == DFGPU_UINT32) mode = 3;   // (the low 32 bits of the cell)
+    else if (is_bitwise(a.func) && vf.type == DFGPU_BOOL) mode = 6;
     if (is_variance(a.func)) {
       if (A.partial_out()) {
         // state_fields of VAR / STDDEV: [count: UInt64, mean: Float64, m2: Float64] (variance.rs), an empty group's mean and m2 are 0
@@ -4867,7 +4998,8 @@ static Table agg_emit(Aggregate& A) {
     bool nullable = a.func != DFGPU_AGG_COUNT && !a.seen_all;
     // partial state field names: format_state_name (expr/src/utils.rs:1416) — `name[sum]` (sum.rs:293-299), `name[count]`
     // (count.rs:317-323), `name[value]` for MIN / MAX (the default AggregateUDFImpl::state_fields, expr/src/udaf.rs:579-585)
-    const std::string out_name = !A.partial_out() ? a.name : a.name + (a.func == DFGPU_AGG_SUM ? "[sum]" : a.func == DFGPU_AGG_COUNT ? "[count]" : "[value]");
+    // BIT_* / BOOL_*: one state column of the argument's type, named like the aggregate
+    const std::string out_name = !A.partial_out() || is_bitwise(a.func) ? a.name : a.name + (a.func == DFGPU_AGG_SUM ? "[sum]" : a.func == DFGPU_AGG_COUNT ? "[count]" : "[value]");
     if (vf.type == DFGPU_DECIMAL128 && p.kind != ACC_SUM_I128) {
       // widen the i64 MIN/MAX accumulator to i128: hi = sign(lo)
       Column c = emit_column(fld(DFGPU_INT64), out_name, 0, a.lo, nullptr, a.seen, G, nullable);
@@ -4956,7 +5088,7 @@ int dfgpu_agg_create(int mode, const dfgpu_expr* group_by, const char* const* gr
     for (int k = 0; k < n_aggs; k++) {
       AggState a;
       a.func = aggs[k].func;
-      DFGPU_CHECK(a.func >= DFGPU_AGG_SUM && a.func <= DFGPU_AGG_STDDEV_POP, "unsupported aggregate function");
+      DFGPU_CHECK(a.func >= DFGPU_AGG_SUM && a.func <= DFGPU_AGG_BOOL_OR, "unsupported aggregate function");
       a.has_arg = aggs[k].has_arg != 0;
       DFGPU_CHECK(a.has_arg || a.func == DFGPU_AGG_COUNT, "only COUNT may omit its argument");
       if (a.has_arg && aggs[k].arg.nodes) {

@@ -18,8 +18,12 @@ NULL_EQUALITY = {"NullEqualsNothing": 0, "NullEqualsNull": 1}
 AGG_MODES = {"Partial": 0, "Final": 1, "FinalPartitioned": 2, "Single": 3, "SinglePartitioned": 4, "PartialReduce": 5}
 AGG_FUNCS = {"sum": 0, "min": 1, "max": 2, "count": 3, "avg": 4, "var": 5, "var_pop": 6, "stddev": 7, "stddev_pop": 8,
              # the aliases the reference registers (functions-aggregate/src/variance.rs, stddev.rs)
-             "var_samp": 5, "var_sample": 5, "var_population": 6, "stddev_samp": 7}
-VARIANCE_FUNCS = frozenset(f for f, i in AGG_FUNCS.items() if i >= 5)
+             "var_samp": 5, "var_sample": 5, "var_population": 6, "stddev_samp": 7,
+             # bit_and_or_xor.rs, bool_and_or.rs: one fixed-width state per group, exact
+             "bit_and": 9, "bit_or": 10, "bit_xor": 11, "bool_and": 12, "bool_or": 13}
+VARIANCE_FUNCS = frozenset(f for f, i in AGG_FUNCS.items() if 5 <= i <= 8)
+BITWISE_FUNCS = frozenset(("bit_and", "bit_or", "bit_xor"))
+BOOLEAN_FUNCS = frozenset(("bool_and", "bool_or"))
 GPU_MIN_KEY_DENSITY = 1.0 / 64.0      # DFGPU_DEFAULT_MIN_KEY_DENSITY (include/dfgpu.h); the reference's CPU default is 0.15
 TABLE_MODES = {"auto": 0, "hash_map": 1, "array_map": 2, "rank_map": 3}
 PROBE_MODES = {"auto": 0, "two_pass": 1, "single_pass_ordered": 2, "single_pass_unordered": 3, "order_not_needed": 4}

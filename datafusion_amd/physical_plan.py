@@ -772,7 +772,7 @@ def plan_schema(node):
                         fields.append(pa.field(n + "[count]", pa.uint64()))
                         # avg_sum_data_type (average.rs:131-172): the input precision + 13 digits, never narrower than Decimal128's 38
                         fields.append(pa.field(n + "[sum]", pa.decimal128(38, t.scale) if pa.types.is_decimal128(t) else pa.float64()))
-                    else:
+                    else:   # one state column (bit_* / bool_*: of the argument's type, named like the aggregate)
                         fields.append(pa.field(n, _agg_type(func, t)))
                 else:
                     fields.append(pa.field(n, _agg_type(func, t)))
@@ -803,7 +803,7 @@ def _agg_type(func, t):
         return pa.decimal128(min(38, t.precision + 4), min(38, t.scale + 4)) if pa.types.is_decimal128(t) else pa.float64()   # average.rs:219-252
     if func in ops.VARIANCE_FUNCS:
         return pa.float64()     # variance.rs / stddev.rs return_type
-    return t    # min / max
+    return t    # min / max; bit_and / bit_or / bit_xor and bool_and / bool_or: the argument's type (bit_and_or_xor.rs, bool_and_or.rs)
 
 
 def _key_bits(t):
@@ -853,6 +853,12 @@ def unsupported_reason(node):
                     return f"{func.upper()}({n}) over {t} is not supported on the GPU path"
                 if func in ops.VARIANCE_FUNCS and t not in (pa.float64(), pa.int32(), pa.int64()):
                     # aggregate.hip plan_for: the device reads a Float64, Int32 or Int64 argument (the planner casts to Float64)
+                    return f"{func.upper()}({n}) over {t} is not supported on the GPU path"
+                if func in ops.BITWISE_FUNCS and t not in (pa.int32(), pa.int64(), pa.uint8(), pa.uint32(), pa.uint64()):
+                    # aggregate.hip plan_for: BIT_AND / BIT_OR / BIT_XOR take the integer types the device has
+                    return f"{func.upper()}({n}) over {t} is not supported on the GPU path"
+                if func in ops.BOOLEAN_FUNCS and not pa.types.is_boolean(t):
+                    # aggregate.hip plan_for: BOOL_AND / BOOL_OR take a Boolean
                     return f"{func.upper()}({n}) over {t} is not supported on the GPU path"
         finally:
             empty.free()

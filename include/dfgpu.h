@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define DFGPU_ABI_VERSION 14
+#define DFGPU_ABI_VERSION 15
 
 /* Arrow C Data Interface (https://arrow.apache.org/docs/format/CDataInterface.html) */
 #ifndef ARROW_C_DATA_INTERFACE
@@ -565,10 +565,15 @@ typedef enum dfgpu_agg_mode {
   DFGPU_AGG_PARTIAL_REDUCE = 5    /* partial state -> partial state: merges like Final, emits like Partial (mod.rs:340-361) */
 } dfgpu_agg_mode;
 /* VAR_SAMP .. STDDEV_POP (ABI 14): variance.rs / stddev.rs — registered names var, var_pop, stddev, stddev_pop; the argument is
- * Float64, Int32 or Int64 (the planner casts it to Float64), the result Float64 */
+ * Float64, Int32 or Int64 (the planner casts it to Float64), the result Float64.
+ * BIT_AND .. BIT_XOR (ABI 15): bit_and_or_xor.rs — registered names bit_and, bit_or, bit_xor; the argument is Int32, Int64, UInt8,
+ * UInt32 or UInt64, the result the argument's type.  BOOL_AND / BOOL_OR (ABI 15): bool_and_or.rs — bool_and, bool_or; argument and
+ * result are Boolean.  NULL arguments are skipped; a group without a non-NULL value gives NULL.  Any other argument type is refused
+ * ("... is not supported on the GPU path"); DISTINCT is not taken. */
 typedef enum dfgpu_agg_func {
   DFGPU_AGG_SUM = 0, DFGPU_AGG_MIN = 1, DFGPU_AGG_MAX = 2, DFGPU_AGG_COUNT = 3, DFGPU_AGG_AVG = 4,
-  DFGPU_AGG_VAR_SAMP = 5, DFGPU_AGG_VAR_POP = 6, DFGPU_AGG_STDDEV_SAMP = 7, DFGPU_AGG_STDDEV_POP = 8
+  DFGPU_AGG_VAR_SAMP = 5, DFGPU_AGG_VAR_POP = 6, DFGPU_AGG_STDDEV_SAMP = 7, DFGPU_AGG_STDDEV_POP = 8,
+  DFGPU_AGG_BIT_AND = 9, DFGPU_AGG_BIT_OR = 10, DFGPU_AGG_BIT_XOR = 11, DFGPU_AGG_BOOL_AND = 12, DFGPU_AGG_BOOL_OR = 13
 } dfgpu_agg_func;
 typedef struct dfgpu_agg_spec {
   int32_t func;          /* dfgpu_agg_func */
@@ -586,7 +591,9 @@ typedef struct dfgpu_agg_spec {
  * groups_accumulator.rs:105).  In FINAL modes the input is the partial-state schema the
  * reference uses (group cols, then per aggregate: SUM -> [sum]; COUNT -> [count];
  * MIN/MAX -> [value]; AVG -> [count u64, sum]; sum.rs:281-301, average.rs:317-360; VAR_* / STDDEV_* -> [count u64,
- * mean f64, m2 f64], m2 = the sum of squared deviations from the mean, variance.rs VarianceGroupsAccumulator::state) and
+ * mean f64, m2 f64], m2 = the sum of squared deviations from the mean, variance.rs VarianceGroupsAccumulator::state;
+ * BIT_* / BOOL_* -> one nullable column of the argument's type, named like the aggregate, NULL where the group saw no value —
+ * Final modes merge it with the same operation, XOR with XOR) and
  * `arg`/`group_by` expressions are ignored beyond their count. */
 int dfgpu_agg_create(int mode, const dfgpu_expr* group_by, const char* const* group_names, int n_group,
                      const dfgpu_agg_spec* aggs, int n_aggs, dfgpu_agg_t* out);

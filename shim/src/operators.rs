@@ -49,7 +49,7 @@ pub enum GpuOp {
 
 #[derive(Debug, Clone)]
 pub struct AggSpec {
-    pub func: i32, // dfgpu_agg_func: SUM, AVG, COUNT, MIN, MAX
+    pub func: i32, // dfgpu_agg_func: SUM, AVG, COUNT, MIN, MAX, VAR_* / STDDEV_*, BIT_AND / BIT_OR / BIT_XOR, BOOL_AND / BOOL_OR
     pub arg: Option<Arc<Lowered>>,
     pub name: CString,
     pub return_field: sys::dfgpu_field,
@@ -172,6 +172,12 @@ impl GpuUnaryExec {
                 "var_pop" | "var_population" => sys::DFGPU_AGG_VAR_POP,
                 "stddev" | "stddev_samp" => sys::DFGPU_AGG_STDDEV_SAMP,
                 "stddev_pop" => sys::DFGPU_AGG_STDDEV_POP,
+                // bit_and_or_xor.rs / bool_and_or.rs
+                "bit_and" => sys::DFGPU_AGG_BIT_AND,
+                "bit_or" => sys::DFGPU_AGG_BIT_OR,
+                "bit_xor" => sys::DFGPU_AGG_BIT_XOR,
+                "bool_and" => sys::DFGPU_AGG_BOOL_AND,
+                "bool_or" => sys::DFGPU_AGG_BOOL_OR,
                 _ => return None,
             };
             if f.is_distinct() || !f.order_bys().is_empty() || f.expressions().len() > 1 {
@@ -198,6 +204,15 @@ impl GpuUnaryExec {
                 if (sys::DFGPU_AGG_VAR_SAMP..=sys::DFGPU_AGG_STDDEV_POP).contains(&func)
                     && !matches!(arg_type, Some(DataType::Float64 | DataType::Int32 | DataType::Int64))
                 {
+                    return None;
+                }
+                // BIT_AND / BIT_OR / BIT_XOR read the integer types the device has, BOOL_AND / BOOL_OR a Boolean (aggregate.hip plan_for)
+                if (sys::DFGPU_AGG_BIT_AND..=sys::DFGPU_AGG_BIT_XOR).contains(&func)
+                    && !matches!(arg_type, Some(DataType::Int32 | DataType::Int64 | DataType::UInt8 | DataType::UInt32 | DataType::UInt64))
+                {
+                    return None;
+                }
+                if (sys::DFGPU_AGG_BOOL_AND..=sys::DFGPU_AGG_BOOL_OR).contains(&func) && !matches!(arg_type, Some(DataType::Boolean)) {
                     return None;
                 }
             }
