@@ -43,8 +43,48 @@ constexpr uint32_t PROBE_LIMIT = 256;  // longer probe sequence => table too ful
 // accumulator kinds
 // (ACC_AND / ACC_OR / ACC_XOR: bit_and / bit_or / bit_xor over the 64-bit cell, bool_and / bool_or over a 0/1 cell — exact, associative
 // and commutative like the integer sums, so every site folds and merges them with the operation itself)
+// A new kind is described in six places: its row of ACC_KIND_TEXT (what the three source generators write for it), accumulate_cell,
+// acc_identity and acc_fold64 (what the static kernels do with it), the flush of k_dense_accumulate_parts (a switch of its own over
+// totals), and the literal helper block of agg_node_source (that block's enum, identity_of, global_accumulate and fold switch).
+// plan_for decides which aggregate gets it.
 enum AccKind : int { ACC_SUM_I64 = 0, ACC_SUM_I128 = 1, ACC_SUM_F64 = 2, ACC_MIN_I64 = 3, ACC_MAX_I64 = 4, ACC_COUNT = 5, ACC_COUNT_STAR = 6,
-                     ACC_AND = 7, ACC_OR = 8, ACC_XOR = 9 };
+                     ACC_AND = 7, ACC_OR = 8, ACC_XOR = 9, ACC_KIND_COUNT = 10 };
+// The text of a one-cell 64-bit kind in a generated source (agg_node_source, agg_dense_node_source, agg_runs_node_source): the running
+// total `t` of C type `type`; a U64 operand x enters it as from_u64[0] x from_u64[1] and `t` goes back to a U64 cell as
+// to_u64[0] t to_u64[1]; `neutral` as the scans spell it; the atomic and the cast it wants of the U64* cell; the segmented and the
+// whole-wave scan; the statement that folds `e` into `t`; `bitwise`: the scans are not in every source (SEG_AND_XOR_SOURCE).
+// Rows without text are the kinds whose STRUCTURE differs, so that each generator has an arm for them: the 128-bit sum and the counts.
+struct AccKindText {
+  const char* type;
+  const char* from_u64[2];
+  const char* to_u64[2];
+  const char* neutral;
+  const char* atomic;
+  const char* cell_cast;
+  const char* seg;
+  const char* all;   // (null: ACC_SUM_I64, which the runs node sums as a difference of DPP prefixes)
+  const char* fold;
+  bool bitwise;
+};
+constexpr AccKindText ACC_KIND_TEXT[] = {
+    /* ACC_SUM_I64    */ {"U64", {"", ""}, {"", ""}, "0ull", "atomicAdd", "", "seg_add_u64", nullptr, "t += e", false},
+    /* ACC_SUM_I128   */ {},
+    /* ACC_SUM_F64    */ {"double", {"__longlong_as_double((long long)", ")"}, {"(U64)__double_as_longlong(", ")"}, "0.0", "atomicAdd", "reinterpret_cast<double*>", "seg_add_f64", "all_add_f64", "t += e", false},
+    /* ACC_MIN_I64    */ {"long long", {"(long long)", ""}, {"(U64)", ""}, "0x7fffffffffffffffll", "atomicMin", "reinterpret_cast<long long*>", "seg_min_i64", "all_min_i64", "t = e < t ? e : t", false},
+    /* ACC_MAX_I64    */ {"long long", {"(long long)", ""}, {"(U64)", ""}, "(-0x7fffffffffffffffll - 1)", "atomicMax", "reinterpret_cast<long long*>", "seg_max_i64", "all_max_i64", "t = e > t ? e : t", false},
+    /* ACC_COUNT      */ {},
+    /* ACC_COUNT_STAR */ {},
+    /* ACC_AND        */ {"U64", {"", ""}, {"", ""}, "~0ull", "atomicAnd", "", "seg_and_u64", "all_and_u64", "t &= e", true},
+    /* ACC_OR         */ {"U64", {"", ""}, {"", ""}, "0ull", "atomicOr", "", "seg_or_u64", "all_or_u64", "t |= e", true},
+    /* ACC_XOR        */ {"U64", {"", ""}, {"", ""}, "0ull", "atomicXor", "", "seg_xor_u64", "all_xor_u64", "t ^= e", true},
+};
+static_assert(sizeof(ACC_KIND_TEXT) / sizeof(ACC_KIND_TEXT[0]) == ACC_KIND_COUNT, "one row of ACC_KIND_TEXT per AccKind");
+// the row of a kind a generator has no arm of its own for; a kind without one fails here, loudly
+static const AccKindText& acc_kind_text(int kind, const char* node) {
+  if (kind < 0 || kind >= ACC_KIND_COUNT || !ACC_KIND_TEXT[kind].type) throw Error(std::string(node) + ": accumulator kind " + std::to_string(kind) + " has no generated form");
+  return ACC_KIND_TEXT[kind];
+}
+static bool is_bitwise_kind(int kind) { return kind >= 0 && kind < ACC_KIND_COUNT && ACC_KIND_TEXT[kind].bitwise; }
 // how a value is loaded & widened (VAL_BIT: a bit-packed Boolean column, row i = bit i -> 0 / 1)
 enum ValKind : int { VAL_I32 = 0, VAL_I64 = 1, VAL_I128 = 2, VAL_F64 = 3, VAL_U8 = 4, VAL_F64_ORDERED = 5, VAL_I32_TO_F64 = 6, VAL_I64_TO_F64 = 7, VAL_U32 = 8, VAL_U64 = 9,
                      VAL_BIT = 10 };
@@ -204,6 +244,21 @@ __device__ __forceinline__ unsigned long long acc_fold64(int kind, unsigned long
     case ACC_XOR: return a ^ v;
     default: return a + v;  // ACC_SUM_I64, ACC_COUNT, ACC_COUNT_STAR
   }
+}
+// the kind that merges a TOTAL of `kind` into a cell: a count's total is added, every other kind merges with itself
+// (handed the descriptor's field in its own type, int or int16_t: widened inside, the compares of a 16-bit field compile to the
+// instructions of the spelled-out form this replaces; widened by the caller they do not — profiles/acc_kind_table.md)
+template <typename K>
+__host__ __device__ __forceinline__ int acc_merge_kind(K field) {
+  int kind = field;
+  if (kind == ACC_COUNT || kind == ACC_COUNT_STAR) kind = ACC_SUM_I64;
+  return kind;
+}
+// the low word of a running 128-bit sum += v; returns the carry its high word is owed: (lo, hi) += (vlo, vhi) is hi += vhi + add_carry(lo, vlo)
+__device__ __forceinline__ unsigned long long add_carry(unsigned long long& lo, unsigned long long v) {
+  const unsigned long long old = lo;
+  lo += v;
+  return lo < old ? 1ull : 0ull;
 }
 
 // ------------------------------------------------------------------------------ intern
@@ -696,9 +751,7 @@ __global__ __launch_bounds__(BLOCK) void k_accumulate_lds(InternCtx c, const uin
     int within = x % per_rep;
     int k = within / ngroups, gid = within % ngroups;
     const AccDesc& d = accs.a[k];
-    int kind = d.kind;
-    if (kind == ACC_COUNT || kind == ACC_COUNT_STAR) kind = ACC_SUM_I64;  // merge counts by adding
-    accumulate_cell(kind, d.acc_lo + gid, d.acc_hi ? d.acc_hi + gid : nullptr, s_lo[x], s_hi[x]);
+    accumulate_cell(acc_merge_kind(d.kind), d.acc_lo + gid, d.acc_hi ? d.acc_hi + gid : nullptr, s_lo[x], s_hi[x]);
     if (d.seen) d.seen[gid] = 1u;
   }
 }
@@ -1217,6 +1270,8 @@ static AccPlan plan_for(int func, const dfgpu_field& t, bool merging_counts) {
   throw Error("aggregate over " + type_name(t) + " is not supported on the GPU path");
 }
 static bool is_bitwise(int func) { return func >= DFGPU_AGG_BIT_AND && func <= DFGPU_AGG_BOOL_OR; }
+// what an aggregate over raw rows accumulates: the planned kind, except that COUNT(*) has no argument whose NULLs it would skip
+static int acc_kind_of(const AggState& a, const AccPlan& p) { return a.func == DFGPU_AGG_COUNT && !a.has_arg ? ACC_COUNT_STAR : p.kind; }
 
 // MIN / MAX over Decimal128 wider than 18 digits: is every (valid) value representable in 64 bits?
 static bool wide_minmax(int func, const dfgpu_field& t) {
@@ -1360,7 +1415,7 @@ __global__ __launch_bounds__(BLOCK) void k_agg_fused(RowProgram p, int n_prologu
     for (int x = threadIdx.x; x < per; x += BLOCK) {
       const int k = x / ngroups, gid = x % ngroups;
       const FusedAcc& d = accs.a[k];
-      int kind = d.kind;
+      const int kind = d.kind;
       bool any = false;
       unsigned long long lo = acc_identity(kind), hi = 0ull;
       for (int q = 0; q < nrep; q++) {
@@ -1368,12 +1423,11 @@ __global__ __launch_bounds__(BLOCK) void k_agg_fused(RowProgram p, int n_prologu
         if (!s_seen[cell]) continue;
         any = true;
         const unsigned long long vlo = s_lo[cell], vhi = s_hi[cell];
-        if (kind == ACC_SUM_I128) { unsigned long long o = lo; lo += vlo; hi += vhi + (lo < o ? 1ull : 0ull); }
+        if (kind == ACC_SUM_I128) hi += vhi + add_carry(lo, vlo);
         else lo = acc_fold64(kind, lo, vlo);
       }
       if (!any) continue;
-      if (kind == ACC_COUNT || kind == ACC_COUNT_STAR) kind = ACC_SUM_I64;  // merge counts by adding
-      accumulate_cell(kind, d.acc_lo + gid, d.acc_hi ? d.acc_hi + gid : nullptr, lo, hi);
+      accumulate_cell(acc_merge_kind(d.kind), d.acc_lo + gid, d.acc_hi ? d.acc_hi + gid : nullptr, lo, hi);
       if (d.seen) d.seen[gid] = 1u;
     }
   }
@@ -1492,19 +1546,8 @@ __global__ __launch_bounds__(BLOCK) void k_agg_fused_tile(TileProgram p, int pre
         }
         seen |= 1u << k;
         unsigned long long* c = s_cell + d.cell0 * plane + base;
-        switch (d.kind) {
-          case ACC_SUM_I128: lds_add_limbs(c, plane, lo, hi); break;
-          case ACC_SUM_I64: atomicAdd(c, (unsigned long long)lo); break;
-          case ACC_SUM_F64: atomicAdd(reinterpret_cast<double*>(c), __longlong_as_double((long long)lo)); break;
-          case ACC_MIN_I64: atomicMin(reinterpret_cast<long long*>(c), (long long)lo); break;
-          case ACC_MAX_I64: atomicMax(reinterpret_cast<long long*>(c), (long long)lo); break;
-          case ACC_AND: atomicAnd(c, (unsigned long long)lo); break;
-          case ACC_OR: atomicOr(c, (unsigned long long)lo); break;
-          case ACC_XOR: atomicXor(c, (unsigned long long)lo); break;
-          case ACC_COUNT:
-          case ACC_COUNT_STAR: atomicAdd(c, 1ull); break;
-          default: break;
-        }
+        if (d.kind == ACC_SUM_I128) lds_add_limbs(c, plane, lo, hi);   // (three limb cells, no carry between them)
+        else accumulate_cell(d.kind, c, nullptr, lo, hi);
       }
       if (seen & ~s_seen[base]) atomicOr(&s_seen[base], seen);
     } else {
@@ -1551,7 +1594,7 @@ __global__ __launch_bounds__(BLOCK) void k_agg_fused_tile(TileProgram p, int pre
       hi = (unsigned long long)(v >> 64);
     } else {
       for (int q = 0; q < nrep; q++) lo = acc_fold64(kind, lo, c[q]);
-      if (kind == ACC_COUNT || kind == ACC_COUNT_STAR) kind = ACC_SUM_I64;  // merge counts by adding
+      kind = acc_merge_kind(d.kind);
     }
     accumulate_cell(kind, d.tmp_lo + key, d.tmp_hi ? d.tmp_hi + key : nullptr, lo, hi);
     atomicOr(&g_seen[key], 1u << k);
@@ -1573,9 +1616,7 @@ __device__ __forceinline__ void small_merge_one(int e, uint32_t key, uint32_t gi
   const int k = dst.src[e];
   if (!((g_seen[key] >> k) & 1u)) return;
   const SmallAcc& d = accs.a[k];
-  int kind = d.kind;
-  if (kind == ACC_COUNT || kind == ACC_COUNT_STAR) kind = ACC_SUM_I64;
-  accumulate_cell(kind, dst.lo[e] + gid, dst.hi[e] ? dst.hi[e] + gid : nullptr, d.tmp_lo[key], d.tmp_hi ? d.tmp_hi[key] : 0ull);
+  accumulate_cell(acc_merge_kind(d.kind), dst.lo[e] + gid, dst.hi[e] ? dst.hi[e] + gid : nullptr, d.tmp_lo[key], d.tmp_hi ? d.tmp_hi[key] : 0ull);
   if (dst.seen[e]) dst.seen[e][gid] = 1u;
 }
 __global__ __launch_bounds__(BLOCK) void k_small_merge(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ gids, int n_keys, SmallAccSet accs,
@@ -2118,7 +2159,9 @@ __device__ __forceinline__ void global_accumulate(int kind, U64* lo_cell, U64* h
   }
 }
 )SRC";
-  static_assert(ACC_AND == 7 && ACC_OR == 8 && ACC_XOR == 9 && ACC_COUNT == 5 && ACC_COUNT_STAR == 6, "the enum of the generated source repeats AccKind");
+  static_assert(ACC_SUM_I64 == 0 && ACC_SUM_I128 == 1 && ACC_SUM_F64 == 2 && ACC_MIN_I64 == 3 && ACC_MAX_I64 == 4 && ACC_COUNT == 5 && ACC_COUNT_STAR == 6 && ACC_AND == 7 &&
+                    ACC_OR == 8 && ACC_XOR == 9 && ACC_KIND_COUNT == 10,
+                "the enum of the generated source repeats AccKind");
   src += "#define NACC " + S(accs.n) + "\n#define NCELL " + S(accs.ncell) + "\n";
   src += "__device__ __forceinline__ int acc_kind(int k) { switch (k) {";
   for (int k = 0; k < accs.n; k++) src += " case " + S(k) + ": return " + S(accs.a[k].kind) + ";";
@@ -2173,20 +2216,16 @@ extern "C" __global__ __launch_bounds__(BLOCK) void agg_node(Args a) {
     const std::string c = "(s_cell + " + S(accs.a[k].cell0) + " * plane + base)";
     src += "      " + guard + "{ seen |= " + S(1u << k) + "u; ";
     switch (accs.a[k].kind) {
-      case ACC_SUM_I128:
+      case ACC_SUM_I128:   // three limb cells in LDS, no carry between them
         src += "const U64 lo = " + vlo + ", hi = " + vhi + "; U64* c = " + c + "; atomicAdd(c, lo & LIMB_MASK); atomicAdd(c + plane, ((lo >> 43) | (hi << 21)) & LIMB_MASK); "
                "atomicAdd(c + 2 * plane, (U64)((long long)hi >> 22));";
         break;
-      case ACC_SUM_I64: src += "atomicAdd(" + c + ", " + vlo + ");"; break;
-      case ACC_SUM_F64: src += "atomicAdd(reinterpret_cast<double*>" + c + ", __longlong_as_double((long long)" + vlo + "));"; break;
-      case ACC_MIN_I64: src += "atomicMin(reinterpret_cast<long long*>" + c + ", (long long)" + vlo + ");"; break;
-      case ACC_MAX_I64: src += "atomicMax(reinterpret_cast<long long*>" + c + ", (long long)" + vlo + ");"; break;
-      case ACC_AND: src += "atomicAnd(" + c + ", " + vlo + ");"; break;
-      case ACC_OR: src += "atomicOr(" + c + ", " + vlo + ");"; break;
-      case ACC_XOR: src += "atomicXor(" + c + ", " + vlo + ");"; break;
-      case ACC_COUNT:
+      case ACC_COUNT:   // the counts add one, whatever the value
       case ACC_COUNT_STAR: src += "atomicAdd(" + c + ", 1ull);"; break;
-      default: throw Error("small-domain node: accumulator kind " + S(accs.a[k].kind) + " has no generated form");
+      default: {
+        const AccKindText& t = acc_kind_text(accs.a[k].kind, "small-domain node");
+        src += std::string(t.atomic) + "(" + t.cell_cast + c + ", " + t.from_u64[0] + vlo + t.from_u64[1] + ");";
+      }
     }
     src += " }\n";
   }
@@ -2342,7 +2381,6 @@ __device__ __forceinline__ U64 all_xor_u64(U64 v) {
   return v;
 }
 )SRC";
-static bool is_bitwise_kind(int kind) { return kind == ACC_AND || kind == ACC_OR || kind == ACC_XOR; }
 
 static std::string agg_dense_node_source(const CompiledProgram& cp, int key_val, const std::vector<DenseAcc>& accs) {
   auto S = [](long long v) { return std::to_string(v); };
@@ -2476,41 +2514,19 @@ extern "C" __global__ __launch_bounds__(BLOCK) void dense_accumulate(Args a) {
     // number of contributing rows of the run: the run length unless the value can be NULL
     const std::string cnt = maybe_null ? "seg_add_u64(" + X + "ok ? 1ull : 0ull, head)" : "run_len";
     src += "    {\n      const U64 cnt = " + cnt + ";\n";
+    const std::string mark = "      if (tail && cnt) { seen |= " + S(1ll << k) + "u; ";
     switch (c.kind) {
-      case ACC_SUM_I128:
-        src += "      const u128 t = seg_add_u128(" + X + "ok ? (((u128)" + X + "hi << 64) | " + X + "lo) : (u128)0, head);\n"
-               "      if (tail && cnt) { seen |= " + S(1ll << k) + "u; const U64 lo = (U64)t, hi = (U64)(t >> 64); const U64 old = atomicAdd(" + cell +
-               ", lo); atomicAdd(" + cell + " + a.G, hi + ((old + lo) < old ? 1ull : 0ull)); }\n";
+      case ACC_SUM_I128:   // two cell words, the carry between their atomics
+        src += "      const u128 t = seg_add_u128(" + X + "ok ? (((u128)" + X + "hi << 64) | " + X + "lo) : (u128)0, head);\n" + mark +
+               "const U64 lo = (U64)t, hi = (U64)(t >> 64); const U64 old = atomicAdd(" + cell + ", lo); atomicAdd(" + cell + " + a.G, hi + ((old + lo) < old ? 1ull : 0ull)); }\n";
         break;
-      case ACC_SUM_I64:
-        src += "      const U64 t = seg_add_u64(" + X + "ok ? " + X + "lo : 0ull, head);\n      if (tail && cnt) { seen |= " + S(1ll << k) + "u; atomicAdd(" + cell + ", t); }\n";
-        break;
-      case ACC_SUM_F64:
-        src += "      const double t = seg_add_f64(" + X + "ok ? __longlong_as_double((long long)" + X + "lo) : 0.0, head);\n      if (tail && cnt) { seen |= " +
-               S(1ll << k) + "u; atomicAdd(reinterpret_cast<double*>" + cell + ", t); }\n";
-        break;
-      case ACC_MIN_I64:
-        src += "      const long long t = seg_min_i64(" + X + "ok ? (long long)" + X + "lo : 0x7fffffffffffffffll, head);\n      if (tail && cnt) { seen |= " +
-               S(1ll << k) + "u; atomicMin(reinterpret_cast<long long*>" + cell + ", t); }\n";
-        break;
-      case ACC_MAX_I64:
-        src += "      const long long t = seg_max_i64(" + X + "ok ? (long long)" + X + "lo : (-0x7fffffffffffffffll - 1), head);\n      if (tail && cnt) { seen |= " +
-               S(1ll << k) + "u; atomicMax(reinterpret_cast<long long*>" + cell + ", t); }\n";
-        break;
-      case ACC_AND:
-        src += "      const U64 t = seg_and_u64(" + X + "ok ? " + X + "lo : ~0ull, head);\n      if (tail && cnt) { seen |= " + S(1ll << k) + "u; atomicAnd(" + cell + ", t); }\n";
-        break;
-      case ACC_OR:
-        src += "      const U64 t = seg_or_u64(" + X + "ok ? " + X + "lo : 0ull, head);\n      if (tail && cnt) { seen |= " + S(1ll << k) + "u; atomicOr(" + cell + ", t); }\n";
-        break;
-      case ACC_XOR:
-        src += "      const U64 t = seg_xor_u64(" + X + "ok ? " + X + "lo : 0ull, head);\n      if (tail && cnt) { seen |= " + S(1ll << k) + "u; atomicXor(" + cell + ", t); }\n";
-        break;
-      case ACC_COUNT:
-      case ACC_COUNT_STAR:
-        src += "      if (tail && cnt) { seen |= " + S(1ll << k) + "u; atomicAdd(" + cell + ", cnt); }\n";
-        break;
-      default: throw Error("dense-key node: accumulator kind " + S(c.kind) + " has no generated form");
+      case ACC_COUNT:   // the counts add the number of contributing rows: no scan of their own
+      case ACC_COUNT_STAR: src += mark + "atomicAdd(" + cell + ", cnt); }\n"; break;
+      default: {
+        const AccKindText& t = acc_kind_text(c.kind, "dense-key node");
+        src += std::string("      const ") + t.type + " t = " + t.seg + "(" + X + "ok ? " + t.from_u64[0] + X + "lo" + t.from_u64[1] + " : " + t.neutral + ", head);\n" + mark + t.atomic + "(" +
+               t.cell_cast + cell + ", t); }\n";
+      }
     }
     src += "    }\n";
   }
@@ -3297,9 +3313,7 @@ __global__ __launch_bounds__(BLOCK) void k_merge_group_totals(const uint32_t* __
       switch (a.kind) {
         case ACC_SUM_I128: {
           const unsigned long long hi = cells_v[(int64_t)(a.cell + 1) * vstride + g];
-          const unsigned long long old = a.acc_lo[g];
-          a.acc_lo[g] = old + v;
-          a.acc_hi[g] += hi + ((old + v) < old ? 1ull : 0ull);
+          a.acc_hi[g] += hi + add_carry(a.acc_lo[g], v);
           break;
         }
         default: a.acc_lo[g] = acc_fold64(a.kind, a.acc_lo[g], v); break;   // (AND / OR / XOR fold like the sums and the counts: with the operation)
@@ -3363,7 +3377,7 @@ static bool fused_general_partitioned(Aggregate& A, const Table& in, const std::
   for (size_t k = 0; k < A.aggs.size(); k++) {
     AggState& a = A.aggs[k];
     AccDesc d{};
-    d.kind = (a.func == DFGPU_AGG_COUNT && !a.has_arg) ? ACC_COUNT_STAR : plans[k].kind;
+    d.kind = acc_kind_of(a, plans[k]);
     d.val = plans[k].val;
     if (a.has_arg) {
       int c = -1;
@@ -3439,7 +3453,7 @@ static std::vector<AccEntry> accumulator_entries(const Aggregate& A, const Compi
   for (size_t k = 0; k < A.aggs.size(); k++) {
     const AggState& a = A.aggs[k];
     const dfgpu_field t = a.typed ? a.in_type : (a.has_arg ? cp.out_types[(size_t)arg_out[k]] : fld(DFGPU_INT64));
-    const int kind = (a.func == DFGPU_AGG_COUNT && !a.has_arg) ? ACC_COUNT_STAR : plan_for(a.func, t, false).kind;
+    const int kind = acc_kind_of(a, plan_for(a.func, t, false));
     const int val = a.has_arg ? cp.src_out_vals[(size_t)arg_out[k]] : -1;
     entries.push_back({(int)k, false, kind, val, t});
     if (a.func == DFGPU_AGG_AVG) entries.push_back({(int)k, true, ACC_COUNT, val, t});
@@ -3959,7 +3973,7 @@ extern "C" __global__ __launch_bounds__(BLOCK) void runs_accumulate(Args a) {
                seen_plain + " }\n"
                "      else if (atom && cnt) { " + add128 + " " + seen_atom + " }\n";
         break;
-      case ACC_SUM_I64:
+      case ACC_SUM_I64:   // wrapping integers: a difference of DPP prefixes instead of a segmented scan
         src += "      const U64 P = scan_u64(Xok" + ks + " ? Xlo" + ks + " : 0ull);\n"
                "      const U64 Pp = lane_u64(P, hp);\n"
                "      U64 t = P - (h ? Pp : 0ull);\n"
@@ -3967,41 +3981,20 @@ extern "C" __global__ __launch_bounds__(BLOCK) void runs_accumulate(Args a) {
                "      if (plain) { " + cell + "[g] = t; " + seen_plain + " }\n"
                "      else if (atom && cnt) { atomicAdd(" + cell + " + g, t); " + seen_atom + " }\n";
         break;
-      case ACC_SUM_F64:  // floating point: a difference of prefixes would cancel, so the run is summed by a segmented scan
-        src += "      double t = seg_add_f64(Xok" + ks + " ? __longlong_as_double((long long)Xlo" + ks + ") : 0.0, head);\n"
-               "      if (ext) { const double e = all_add_f64(Eok" + ks + " ? __longlong_as_double((long long)Elo" + ks + ") : 0.0); if (lane_ == 63) t += e; }\n"
-               "      if (plain) { " + cell + "[g] = (U64)__double_as_longlong(t); " + seen_plain + " }\n"
-               "      else if (atom && cnt) { atomicAdd(reinterpret_cast<double*>(" + cell + " + g), t); " + seen_atom + " }\n";
-        break;
-      case ACC_MIN_I64:
-        src += "      long long t = seg_min_i64(Xok" + ks + " ? (long long)Xlo" + ks + " : 0x7fffffffffffffffll, head);\n"
-               "      if (ext) { const long long e = all_min_i64(Eok" + ks + " ? (long long)Elo" + ks + " : 0x7fffffffffffffffll); if (lane_ == 63) t = e < t ? e : t; }\n"
-               "      if (plain) { " + cell + "[g] = (U64)t; " + seen_plain + " }\n"
-               "      else if (atom && cnt) { atomicMin(reinterpret_cast<long long*>(" + cell + " + g), t); " + seen_atom + " }\n";
-        break;
-      case ACC_MAX_I64:
-        src += "      long long t = seg_max_i64(Xok" + ks + " ? (long long)Xlo" + ks + " : (-0x7fffffffffffffffll - 1), head);\n"
-               "      if (ext) { const long long e = all_max_i64(Eok" + ks + " ? (long long)Elo" + ks + " : (-0x7fffffffffffffffll - 1)); if (lane_ == 63) t = e > t ? e : t; }\n"
-               "      if (plain) { " + cell + "[g] = (U64)t; " + seen_plain + " }\n"
-               "      else if (atom && cnt) { atomicMax(reinterpret_cast<long long*>(" + cell + " + g), t); " + seen_atom + " }\n";
-        break;
-      case ACC_AND:   // (AND and OR have no inverse: no difference of prefixes, a segmented scan like MIN / MAX)
-      case ACC_OR:
-      case ACC_XOR: {
-        const std::string op = c.kind == ACC_AND ? "and" : c.kind == ACC_OR ? "or" : "xor", sym = c.kind == ACC_AND ? "&" : c.kind == ACC_OR ? "|" : "^";
-        const std::string id = c.kind == ACC_AND ? "~0ull" : "0ull", atomic = c.kind == ACC_AND ? "atomicAnd" : c.kind == ACC_OR ? "atomicOr" : "atomicXor";
-        src += "      U64 t = seg_" + op + "_u64(Xok" + ks + " ? Xlo" + ks + " : " + id + ", head);\n"
-               "      if (ext) { const U64 e = all_" + op + "_u64(Eok" + ks + " ? Elo" + ks + " : " + id + "); if (lane_ == 63) t " + sym + "= e; }\n"
-               "      if (plain) { " + cell + "[g] = t; " + seen_plain + " }\n"
-               "      else if (atom && cnt) { " + atomic + "(" + cell + " + g, t); " + seen_atom + " }\n";
-        break;
-      }
-      case ACC_COUNT:
+      case ACC_COUNT:   // the counts store the number of contributing rows: no scan of their own
       case ACC_COUNT_STAR:
         src += "      if (plain) { " + cell + "[g] = cnt; " + seen_plain + " }\n"
                "      else if (atom && cnt) { atomicAdd(" + cell + " + g, cnt); " + seen_atom + " }\n";
         break;
-      default: throw Error("runs node: accumulator kind " + S(c.kind) + " has no generated form");
+      default: {   // no inverse (MIN / MAX / AND / OR), or one that would cancel (Float64): a segmented scan, and a whole-wave one over the next word's rows
+        const AccKindText& t = acc_kind_text(c.kind, "runs node");
+        const std::string X = std::string(t.from_u64[0]) + "Xlo" + ks + t.from_u64[1], E = std::string(t.from_u64[0]) + "Elo" + ks + t.from_u64[1];
+        const std::string at = *t.cell_cast ? std::string(t.cell_cast) + "(" + cell + " + g)" : cell + " + g";
+        src += std::string("      ") + t.type + " t = " + t.seg + "(Xok" + ks + " ? " + X + " : " + t.neutral + ", head);\n"
+               "      if (ext) { const " + t.type + " e = " + t.all + "(Eok" + ks + " ? " + E + " : " + t.neutral + "); if (lane_ == 63) " + t.fold + "; }\n"
+               "      if (plain) { " + cell + "[g] = " + t.to_u64[0] + "t" + t.to_u64[1] + "; " + seen_plain + " }\n"
+               "      else if (atom && cnt) { " + t.atomic + "(" + at + ", t); " + seen_atom + " }\n";
+      }
     }
     src += "    }\n";
   }
@@ -4532,7 +4525,7 @@ static bool agg_update_fused(Aggregate& A, const Table& in, const dfgpu_expr* pr
   for (size_t k = 0; k < A.aggs.size(); k++) {
     AggState& a = A.aggs[k];
     FusedAcc d{};
-    d.kind = (int16_t)((a.func == DFGPU_AGG_COUNT && !a.has_arg) ? ACC_COUNT_STAR : plans[k].kind);
+    d.kind = (int16_t)acc_kind_of(a, plans[k]);
     d.reg = (int16_t)(a.has_arg ? cp.out_regs[arg_out[k]] : -1);
     d.acc_lo = a.lo->as<unsigned long long>();
     d.acc_hi = a.hi ? a.hi->as<unsigned long long>() : nullptr;
@@ -4693,7 +4686,7 @@ static void agg_update_unfused(Aggregate& A, const Table& in) {
       continue;
     }
     AccDesc d{};
-    d.kind = (a.func == DFGPU_AGG_COUNT && !a.has_arg && !final_mode) ? ACC_COUNT_STAR : p.kind;
+    d.kind = final_mode ? p.kind : acc_kind_of(a, p);   // (a final mode merges counts: its COUNT(*) has a state column)
     d.val = p.val;
     d.values = inputs[k].has_v ? inputs[k].v.ptr() : nullptr;
     d.valid = inputs[k].has_v ? inputs[k].v.valid_words() : nullptr;
