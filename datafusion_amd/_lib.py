@@ -58,7 +58,8 @@ class JoinInfo(C.Structure):
 
 
 class AggSpec(C.Structure):
-    _fields_ = [("func", C.c_int32), ("has_arg", C.c_int32), ("arg", Expr), ("name", C.c_char_p), ("return_field", Field)]
+    _fields_ = [("func", C.c_int32), ("has_arg", C.c_int32), ("arg", Expr), ("name", C.c_char_p), ("return_field", Field),
+                ("has_filter", C.c_int32), ("filter", Expr)]   # ABI 16: FILTER (WHERE ...); a zeroed struct has none
 
 
 class KernelStat(C.Structure):

@@ -1085,6 +1085,15 @@ struct AggState {
   std::vector<dfgpu_expr_node> nodes;
   int root = 0;
   std::string name;
+  // FILTER (WHERE ...) of this aggregate (raw modes only: a final mode is handed none, like `arg`).  Everything below dfgpu_agg_create
+  // reads a filtered aggregate as one whose argument is NULL wherever the filter is not TRUE: the row programs through RP_KEEP_IF
+  // (compile_agg_arguments), the column-at-a-time path through the argument's validity (filtered_validity); COUNT(*) counts the
+  // filter's truth (acc_kind_of).  The groups are still created by every row.
+  bool has_filter = false;
+  std::vector<dfgpu_expr_node> filter_nodes;
+  int filter_root = 0;
+  std::string filter_pool;   // the bytes of the filter's string literals
+  dfgpu_expr filter() const { return dfgpu_expr{filter_nodes.data(), (int)filter_nodes.size(), filter_root, filter_pool.empty() ? nullptr : filter_pool.data()}; }
   dfgpu_field in_type{};  // argument type (raw modes) / state value type (final modes)
   dfgpu_field ret{};      // planner-declared return type (type 0 = derive from in_type)
   bool typed = false;
@@ -1125,6 +1134,11 @@ struct Aggregate {
   bool partial_out() const { return mode == DFGPU_AGG_PARTIAL || mode == DFGPU_AGG_PARTIAL_REDUCE; }
 };
 
+static bool any_filtered(const Aggregate& A) {
+  for (const AggState& a : A.aggs)
+    if (a.has_filter) return true;
+  return false;
+}
 // the calling thread moves to the device the aggregate's state lives on
 static Aggregate* unwrap_agg(dfgpu_agg_t h) {
   DFGPU_CHECK(h != nullptr, "null aggregate handle");
@@ -1270,8 +1284,9 @@ static AccPlan plan_for(int func, const dfgpu_field& t, bool merging_counts) {
   throw Error("aggregate over " + type_name(t) + " is not supported on the GPU path");
 }
 static bool is_bitwise(int func) { return func >= DFGPU_AGG_BIT_AND && func <= DFGPU_AGG_BOOL_OR; }
-// what an aggregate over raw rows accumulates: the planned kind, except that COUNT(*) has no argument whose NULLs it would skip
-static int acc_kind_of(const AggState& a, const AccPlan& p) { return a.func == DFGPU_AGG_COUNT && !a.has_arg ? ACC_COUNT_STAR : p.kind; }
+// what an aggregate over raw rows accumulates: the planned kind, except that COUNT(*) has no argument whose NULLs it would skip —
+// unless it has a FILTER: then it is ACC_COUNT over the filter's truth, the value that is NULL wherever the filter is not TRUE
+static int acc_kind_of(const AggState& a, const AccPlan& p) { return a.func == DFGPU_AGG_COUNT && !a.has_arg && !a.has_filter ? ACC_COUNT_STAR : p.kind; }
 
 // MIN / MAX over Decimal128 wider than 18 digits: is every (valid) value representable in 64 bits?
 static bool wide_minmax(int func, const dfgpu_field& t) {
@@ -1650,6 +1665,31 @@ __global__ __launch_bounds__(BLOCK) void k_and_words(const uint64_t* __restrict_
 }
 void and_bitmaps(const uint64_t* a, const uint64_t* b, int64_t nw, uint64_t* out) {
   if (nw) k_and_words<<<grid_for(nw, BLOCK), BLOCK, 0, rt().stream>>>(a, b, nw, out);
+}
+
+// agg(x) FILTER (WHERE p), column-at-a-time: the argument keeps its values and gets the validity `values_valid & filter_valid &
+// filter_bits` — one bit per row instead of the value column CASE WHEN p THEN x END writes.  64 rows per word, a lane takes whole words
+// and consecutive lanes consecutive words; a missing validity on either side is all ones; the bits of the tail word beyond n are cleared.
+// Every bitmap holds (n + 63) / 64 words (bitmap_bytes).
+__global__ __launch_bounds__(BLOCK) void k_filter_validity(const uint64_t* __restrict__ values_valid, const uint64_t* __restrict__ filter_valid,
+                                                          const uint64_t* __restrict__ filter_bits, int64_t n, uint64_t* __restrict__ out) {
+  const int64_t nw = (n + 63) >> 6;
+  for (int64_t w = (int64_t)blockIdx.x * BLOCK + threadIdx.x; w < nw; w += (int64_t)gridDim.x * BLOCK) {
+    uint64_t m = filter_bits[w];
+    if (filter_valid) m &= filter_valid[w];
+    if (values_valid) m &= values_valid[w];
+    if (w == nw - 1 && (n & 63)) m &= (1ull << (n & 63)) - 1ull;
+    out[w] = m;
+  }
+}
+static BufPtr filtered_validity(const uint64_t* values_valid, const Column& truth, int64_t n) {
+  BufPtr out = make_buf(bitmap_bytes(std::max<int64_t>(n, 1)));
+  if (n) {
+    ProfileScope ps("agg_filter_validity", (n + 63) / 64 * 8 * (2 + (values_valid ? 1 : 0) + (truth.validity ? 1 : 0)));
+    k_filter_validity<<<grid_for((n + 63) / 64, BLOCK), BLOCK, 0, rt().stream>>>(values_valid, truth.valid_words(), (const uint64_t*)truth.ptr(), n, out->as<uint64_t>());
+    DFGPU_HIP(hipGetLastError());
+  }
+  return out;
 }
 
 static bool g_fusion_enabled = true;
@@ -3228,6 +3268,7 @@ static bool partitioned_accumulate(const void* key, int kt, int64_t n_in, long l
 static bool dense_accumulate_partitioned(const Aggregate& A, const Table& in, const dfgpu_expr* pred, const std::vector<DenseAcc>& accs, const std::vector<int>& acc_col,
                                          const std::vector<int>& acc_val, const std::vector<int>& acc_agg, int ncw, long long kmin, uint64_t range, PartValues& out) {
   // cheap refusals before any argument expression is evaluated
+  if (any_filtered(A)) return false;   // (the rows are moved and read as they lie, no validity is asked: dense_accumulate takes a FILTER)
   if (in.nrows < option_int("agg.partitioned_min_rows", 2 * policy().rows_worth_a_pass()) || range < 4096) return false;
   int kc = -1;
   if (!is_plain_column(A.group_nodes[0], A.group_roots[0], &kc) || kc < 0 || kc >= (int)in.cols.size()) return false;
@@ -3372,6 +3413,7 @@ static bool fused_general_partitioned(Aggregate& A, const Table& in, const std::
   const bool off = !option_on("agg.partitioned", true);
   if (trace_on("agg")) fprintf(stderr, "[agg] fused_general_partitioned: n %lld, G0 %lld, G1 %lld, off %d\n", (long long)n, (long long)G0, (long long)G1, (int)off);
   if (off || n < option_int("agg.partitioned_min_rows", 2 * policy().rows_worth_a_pass()) || G1 < 256) return false;   // (fewer groups: the LDS-replicated cells of the fused kernel)
+  if (any_filtered(A)) return false;   // (the argument columns are read as they stand, no validity is asked: the fused kernel takes a FILTER)
   AccSet accs{};
   std::vector<Column> keep;
   for (size_t k = 0; k < A.aggs.size(); k++) {
@@ -3414,19 +3456,22 @@ static bool fused_general_partitioned(Aggregate& A, const Table& in, const std::
 
 // ---------------------------------------------------------------- front end shared by the specialised nodes and agg_update_fused
 // Every aggregate's argument becomes an output of `comp`, converted to what its accumulator expects (plan_for): AVG over ints
-// sums f64; MIN/MAX(f64) on the ordered key.  Returns the output per aggregate, -1 = no argument.
+// sums f64; MIN/MAX(f64) on the ordered key.  Returns the output per aggregate, -1 = no value (COUNT(*) without a FILTER).
 static std::vector<int> compile_agg_arguments(RowProgramCompiler& comp, const Aggregate& A) {
   std::vector<int> arg_out(A.aggs.size(), -1);
   for (size_t k = 0; k < A.aggs.size(); k++) {
     const AggState& a = A.aggs[k];
-    if (!a.has_arg) continue;
-    dfgpu_expr e{a.nodes.data(), (int)a.nodes.size(), a.root};
-    arg_out[k] = comp.add_output(e);
-    dfgpu_field t = comp.output_type(arg_out[k]);
-    if (a.typed) DFGPU_CHECK(a.in_type.type == t.type, "aggregate argument type changed between batches");
-    AccPlan p = plan_for(a.func, t, false);
-    if (p.val == VAL_I32_TO_F64 || p.val == VAL_I64_TO_F64) comp.convert_output(arg_out[k], RP_I2F, t);
-    else if (p.val == VAL_F64_ORDERED) comp.convert_output(arg_out[k], RP_F64ORD, t);
+    if (a.has_arg) {
+      dfgpu_expr e{a.nodes.data(), (int)a.nodes.size(), a.root};
+      arg_out[k] = comp.add_output(e);
+      dfgpu_field t = comp.output_type(arg_out[k]);
+      if (a.typed) DFGPU_CHECK(a.in_type.type == t.type, "aggregate argument type changed between batches");
+      AccPlan p = plan_for(a.func, t, false);
+      if (p.val == VAL_I32_TO_F64 || p.val == VAL_I64_TO_F64) comp.convert_output(arg_out[k], RP_I2F, t);
+      else if (p.val == VAL_F64_ORDERED) comp.convert_output(arg_out[k], RP_F64ORD, t);
+    }
+    // FILTER: the value is NULL wherever the filter is not TRUE; COUNT(*) FILTER gets the value KEEP_IF(1, filter) to count
+    if (a.has_filter) arg_out[k] = comp.keep_output_if(arg_out[k], a.filter(), "aggregate " + a.name);
   }
   return arg_out;
 }
@@ -3454,7 +3499,7 @@ static std::vector<AccEntry> accumulator_entries(const Aggregate& A, const Compi
     const AggState& a = A.aggs[k];
     const dfgpu_field t = a.typed ? a.in_type : (a.has_arg ? cp.out_types[(size_t)arg_out[k]] : fld(DFGPU_INT64));
     const int kind = acc_kind_of(a, plan_for(a.func, t, false));
-    const int val = a.has_arg ? cp.src_out_vals[(size_t)arg_out[k]] : -1;
+    const int val = arg_out[k] >= 0 ? cp.src_out_vals[(size_t)arg_out[k]] : -1;
     entries.push_back({(int)k, false, kind, val, t});
     if (a.func == DFGPU_AGG_AVG) entries.push_back({(int)k, true, ACC_COUNT, val, t});
   }
@@ -3502,7 +3547,7 @@ static bool agg_update_dense_key_jit(Aggregate& A, const Table& in, const dfgpu_
     if (u == (int)accs.size()) {
       int arg_col = -1;
       accs.push_back({en.kind, en.val, (int)cell_kind.size()});
-      acc_col.push_back(!a.has_arg ? -1 : (is_plain_column(a.nodes, a.root, &arg_col) ? arg_col : -2));
+      acc_col.push_back(a.has_filter ? -2 : !a.has_arg ? -1 : (is_plain_column(a.nodes, a.root, &arg_col) ? arg_col : -2));
       acc_val.push_back(plan_for(a.func, en.type, false).val);
       acc_agg.push_back(en.agg);
       cell_kind.push_back(en.kind == ACC_SUM_I128 ? ACC_SUM_I64 : en.kind);
@@ -4526,7 +4571,7 @@ static bool agg_update_fused(Aggregate& A, const Table& in, const dfgpu_expr* pr
     AggState& a = A.aggs[k];
     FusedAcc d{};
     d.kind = (int16_t)acc_kind_of(a, plans[k]);
-    d.reg = (int16_t)(a.has_arg ? cp.out_regs[arg_out[k]] : -1);
+    d.reg = (int16_t)(arg_out[k] >= 0 ? cp.out_regs[arg_out[k]] : -1);
     d.acc_lo = a.lo->as<unsigned long long>();
     d.acc_hi = a.hi ? a.hi->as<unsigned long long>() : nullptr;
     d.seen = a.seen->as<uint32_t>();
@@ -4582,8 +4627,23 @@ static void agg_update_unfused(Aggregate& A, const Table& in) {
     key_cols.back().name = A.group_names[g];
   }
   // argument / state columns per aggregate
-  struct Inputs { Column v; Column c; Column m2; bool has_v = false, has_c = false; };
+  struct Inputs { Column v; Column c; Column m2; bool has_v = false, has_c = false; BufPtr truth; };   // truth: COUNT(*) FILTER's "argument"
   std::vector<Inputs> inputs(A.aggs.size());
+  // FILTER: every distinct filter forest is evaluated once (a pivot repeats a small set of predicates over many aggregates), and so is
+  // its truth bitmap `filter_valid & filter_bits` that aggregates over arguments without NULLs share
+  struct Truth { Column col; BufPtr bits; };
+  std::map<std::string, Truth> truths;
+  auto truth_of = [&](const AggState& a) -> Truth& {
+    std::string key((const char*)a.filter_nodes.data(), a.filter_nodes.size() * sizeof(dfgpu_expr_node));
+    key += '#' + std::to_string(a.filter_root) + '#' + a.filter_pool;
+    auto it = truths.find(key);
+    if (it != truths.end()) return it->second;
+    Datum d = evaluate(a.filter(), in);
+    DFGPU_CHECK(d.col.field.type == DFGPU_BOOL, "aggregate " + a.name + ": the FILTER expression must be Boolean, not " + type_name(d.col.field));
+    Truth t;
+    t.col = datum_to_column(d, n, "");
+    return truths.emplace(key, std::move(t)).first->second;
+  };
   int state_col = ngk;
   for (size_t k = 0; k < A.aggs.size(); k++) {
     AggState& a = A.aggs[k];
@@ -4608,6 +4668,25 @@ static void agg_update_unfused(Aggregate& A, const Table& in) {
       dfgpu_expr e{a.nodes.data(), (int)a.nodes.size(), a.root};
       inputs[k].v = datum_to_column(evaluate(e, in), n, a.name);
       inputs[k].has_v = true;
+    }
+    if (!final_mode && a.has_filter) {
+      // the argument keeps its value buffer and gets the validity that the filter clears; nothing is copied or rewritten
+      Truth& t = truth_of(a);
+      const uint64_t* vv = inputs[k].has_v ? inputs[k].v.valid_words() : nullptr;
+      BufPtr m;
+      if (vv) {
+        m = filtered_validity(vv, t.col, n);
+      } else {
+        if (!t.bits) t.bits = filtered_validity(nullptr, t.col, n);
+        m = t.bits;
+      }
+      if (inputs[k].has_v) {
+        inputs[k].v.validity = m;
+        inputs[k].v.null_count = -1;
+        inputs[k].v.stats = nullptr;
+      } else {
+        inputs[k].truth = m;
+      }
     }
     if (!a.typed) {
       if (inputs[k].has_v) a.in_type = inputs[k].v.field;
@@ -4689,7 +4768,7 @@ static void agg_update_unfused(Aggregate& A, const Table& in) {
     d.kind = final_mode ? p.kind : acc_kind_of(a, p);   // (a final mode merges counts: its COUNT(*) has a state column)
     d.val = p.val;
     d.values = inputs[k].has_v ? inputs[k].v.ptr() : nullptr;
-    d.valid = inputs[k].has_v ? inputs[k].v.valid_words() : nullptr;
+    d.valid = inputs[k].has_v ? inputs[k].v.valid_words() : inputs[k].truth ? inputs[k].truth->as<uint64_t>() : nullptr;   // (COUNT(*) FILTER: the bitmap alone)
     d.narrow = inputs[k].has_v && (p.val != VAL_I128 || (inputs[k].v.field.type == DFGPU_DECIMAL128 && inputs[k].v.field.precision <= 18)) ? 1 : 0;
     d.acc_lo = a.lo->as<unsigned long long>();
     d.acc_hi = a.hi ? a.hi->as<unsigned long long>() : nullptr;
@@ -5090,6 +5169,21 @@ int dfgpu_agg_create(int mode, const dfgpu_expr* group_by, const char* const* gr
       }
       a.name = aggs[k].name ? aggs[k].name : "";
       a.ret = aggs[k].return_field;
+      // FILTER: raw modes only — the reference hands a Final / PartialReduce accumulator no filter, one given there is ignored like `arg`
+      if (aggs[k].has_filter && !A->final_mode()) {
+        const dfgpu_expr& f = aggs[k].filter;
+        DFGPU_CHECK(f.nodes && f.n_nodes >= 1 && f.root >= 0 && f.root < f.n_nodes, "aggregate " + a.name + ": has_filter is set, but the FILTER expression is empty");
+        a.has_filter = true;
+        a.filter_nodes.assign(f.nodes, f.nodes + f.n_nodes);
+        a.filter_root = f.root;
+        size_t pool = 0;
+        for (const dfgpu_expr_node& nd : a.filter_nodes)
+          if (nd.op == DFGPU_EXPR_LITERAL && nd.field.type == DFGPU_UTF8 && !nd.is_null) pool = std::max(pool, (size_t)(nd.lit_lo + nd.lit_hi));
+        if (pool) {
+          DFGPU_CHECK(f.string_pool != nullptr, "aggregate " + a.name + ": the FILTER expression has string literals, but no string pool");
+          a.filter_pool.assign(f.string_pool, pool);
+        }
+      }
       A->aggs.push_back(std::move(a));
     }
     *out = reinterpret_cast<dfgpu_agg_t>(A.release());

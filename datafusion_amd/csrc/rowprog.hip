@@ -313,6 +313,21 @@ void RowProgramCompiler::convert_output(int out, RpOp op, const dfgpu_field& new
   outs_[out] = RpValue{emit(op, outs_[out].id, -2, 0), new_type};
 }
 
+int RowProgramCompiler::keep_output_if(int out, const dfgpu_expr& filter, const std::string& what) {
+  const RpValue p = lower(filter, filter.root);
+  DFGPU_CHECK(p.type.type == DFGPU_BOOL, what + ": the FILTER expression must be Boolean, not " + type_name(p.type));
+  if (out < 0) {
+    const RpValue one = literal(mk(DFGPU_INT64), 1, 0, false);
+    outs_.push_back(RpValue{emit(RP_KEEP_IF, one.id, p.id, 0), one.type});
+    return (int)outs_.size() - 1;
+  }
+  const RpValue x = outs_[out];
+  dfgpu_field t = x.type;
+  t.nullable = 1;
+  outs_[out] = RpValue{emit(RP_KEEP_IF, x.id, p.id, 0, -1, false, t.type == DFGPU_DECIMAL128 || t.type == DFGPU_UINT64), t};
+  return out;
+}
+
 bool RowProgramCompiler::finish(CompiledProgram& cp, std::string& why) {
   if (failed_) {
     why = why_;
@@ -591,12 +606,14 @@ bool RowProgramCompiler::finish(CompiledProgram& cp, std::string& why) {
         case RP_IS_NOT_NULL: val = "(i128)(!" + NA + ")"; nul = "false"; break;
         case RP_GATE: val = "((" + B + " & 1) ? " + A + " : (i128)0)"; nul = "((" + B + " & 1) && " + NA + ")"; break;
         case RP_MERGE: val = "(" + A + " | " + B + ")"; break;
+        case RP_KEEP_IF: val = A; nul = "(" + NA + " || !kt(" + B + "," + NB + "))"; break;
         default: val = A; nul = NA; break;  // RP_MOV
       }
       switch (x.op) {
         case RP_LIT: maybe_null[(size_t)v] = x.lit_null; break;
         case RP_IS_NULL: case RP_IS_NOT_NULL: maybe_null[(size_t)v] = false; break;
         case RP_GATE: maybe_null[(size_t)v] = maybe_null[(size_t)x.a]; break;
+        case RP_KEEP_IF: maybe_null[(size_t)v] = true; break;   // (a filtered aggregate's argument is nullable whatever its column is)
         default: maybe_null[(size_t)v] = (x.a >= 0 && maybe_null[(size_t)x.a]) || (x.b >= 0 && maybe_null[(size_t)x.b]); break;
       }
       st = "    const i128 " + V(v) + " = " + val + ";\n    const bool " + N(v) + " = " + nul + ";\n";
@@ -612,7 +629,7 @@ bool RowProgramCompiler::finish(CompiledProgram& cp, std::string& why) {
   }
   if (trace_on("rowprog")) {
     static const char* names[] = {"lit", "add", "sub", "mul", "sext32", "sext64", "fadd", "fsub", "fmul", "i2f", "f64ord", "cmp", "fcmp", "and", "or", "not",
-                                  "is_null", "is_not_null", "mov", "gate", "merge", "?", "?"};
+                                  "is_null", "is_not_null", "mov", "gate", "merge", "date_part", "keep_if"};
     fprintf(stderr, "[rowprog] cols=%d regs=%d ins=%d (prologue %d, predicate end %d, pred reg %d)\n", n_cols, cp.n_regs, n_ins, n_prologue, n_pred_end, cp.pred_reg);
     for (int i = 0; i < n_ins; i++)
       fprintf(stderr, "  %2d: r%-2d = %-8s r%-2d r%-2d aux=%u\n", i, P.ins[i].dst, P.ins[i].op < 23 ? names[P.ins[i].op] : "?", P.ins[i].a, P.ins[i].b, P.ins[i].aux);

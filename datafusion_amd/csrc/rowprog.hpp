@@ -46,7 +46,9 @@ enum RpOp : uint8_t {
   // CASE WHEN c THEN x ELSE y END = MERGE(GATE(x, t), GATE(y, NOT t)) with t = c AND (c IS NOT NULL):
   RP_GATE = 19,   // dst <- b is TRUE ? a : (0, not NULL)        (b: a non-NULL Boolean)
   RP_MERGE = 20,  // dst <- a | b bitwise, NULL if either is     (at most one side is non-zero / NULL)
-  RP_DATE_PART = 21  // dst <- date_part(aux: 0 YEAR / 1 MONTH / 2 DAY, Date32 a) as Int32
+  RP_DATE_PART = 21, // dst <- date_part(aux: 0 YEAR / 1 MONTH / 2 DAY, Date32 a) as Int32
+  // agg(x) FILTER (WHERE p): the aggregate's argument is x where p is TRUE and NULL everywhere else (every accumulator skips NULLs)
+  RP_KEEP_IF = 22    // dst <- a, NULL if a is NULL or b is not TRUE (FALSE or NULL); RP_GATE differs: it yields a non-NULL 0
 };
 // how a column is widened into a register
 enum RpLoad : uint8_t { RPL_I32 = 0, RPL_I64 = 1, RPL_U8 = 2, RPL_U32 = 3, RPL_U64 = 4, RPL_I128 = 5, RPL_F64 = 6, RPL_BOOL = 7 };
@@ -240,6 +242,7 @@ __device__ __forceinline__ void rp_exec(const RowProgram& p, int k0, int k1, RpR
       case RP_IS_NOT_NULL: olo = an ? 0ull : 1ull; on = false; break;
       case RP_GATE: { const bool t = (blo & 1) != 0; olo = t ? alo : 0ull; ohi = t ? ahi : 0ull; on = t && an; break; }
       case RP_MERGE: olo = alo | blo; ohi = ahi | bhi; break;
+      case RP_KEEP_IF: olo = alo; ohi = ahi; on = an || bn || !(blo & 1); break;
       default: olo = alo; ohi = ahi; on = an; break;  // RP_MOV
     }
     r.set(rd, olo, ohi);
@@ -385,6 +388,7 @@ __device__ __forceinline__ void tp_exec(const TileProgram& p, int k0, int k1, Ti
       case RP_IS_NOT_NULL: olo = an ? 0ull : 1ull; on = false; break;
       case RP_GATE: { const bool g = (blo & 1) != 0; olo = g ? alo : 0ull; ohi = g ? ahi : 0ull; on = g && an; break; }
       case RP_MERGE: olo = alo | blo; ohi = ahi | bhi; break;
+      case RP_KEEP_IF: olo = alo; ohi = ahi; on = an || bn || !(blo & 1); break;
       default: olo = alo; ohi = ahi; on = an; break;  // RP_MOV
     }
     tp_store(p, t, in.dst, olo, ohi, on);

@@ -54,6 +54,9 @@ class RowProgramCompiler {
   // post-process output `out` with a unary conversion (RP_I2F / RP_F64ORD), in place
   void convert_output(int out, RpOp op, const dfgpu_field& new_type);
   dfgpu_field output_type(int out) const { return outs_[out].type; }
+  // agg(x) FILTER (WHERE filter): output `out` becomes NULL wherever `filter` is not TRUE (RP_KEEP_IF), in place; out < 0 (COUNT(*), no
+  // argument) adds the output KEEP_IF(1, filter) and returns its index.  `what` names the aggregate in the error a non-Boolean filter is.
+  int keep_output_if(int out, const dfgpu_expr& filter, const std::string& what);
   // false (with a reason) when the forest does not fit: too many columns / registers / instructions
   bool finish(CompiledProgram& cp, std::string& why);
 

@@ -239,19 +239,35 @@ def sort(table: DeviceTable, keys, fetch=None) -> DeviceTable:
     return DeviceTable(out)
 
 
+def normalize_aggs(aggs):
+    """an aggregate is (func, arg, name) or (func, arg, name, filter) — filter = the PhysicalExpr of FILTER (WHERE ...), or None;
+    every entry point brings the list to the 4-tuple form once"""
+    out = []
+    for a in aggs or []:
+        if len(a) == 3:
+            out.append((a[0], a[1], a[2], None))
+        elif len(a) == 4:
+            out.append(tuple(a))
+        else:
+            raise ValueError(f"an aggregate is (func, arg, name) or (func, arg, name, filter), not {a!r}")
+    return out
+
+
 class _LoweredAggregate:
     """the C-ABI form of an AggregateExec's expressions (group keys, aggregate arguments, grouping sets): what
     dfgpu_agg_create reads.  Built once per planned node; every execution of the node creates its state from it."""
 
     def __init__(self, mode, input_names, group_by, aggs, dictionaries=None, return_types=None, grouping_sets=None):
         self._keep = []
+        aggs = normalize_aggs(aggs)
         final = mode in ("Final", "FinalPartitioned", "PartialReduce")
         if final:
             # Final modes (and PartialReduce) read the partial-state schema positionally (group columns first); the
             # original argument expressions do not exist in that schema and are not evaluated
             from .expr import Column
             group_by = [(Column(n, i), n) for i, (_, n) in enumerate(group_by)]
-            aggs = [(f, None if f == "count" and e is None else Column("state", 0), n) for f, e, n in aggs]
+            # (the reference hands these modes no filter either: GroupsAccumulator::merge_batch takes none)
+            aggs = [(f, None if f == "count" and e is None else Column("state", 0), n, None) for f, e, n, _ in aggs]
             dictionaries = None
         g_low = [lower(e, input_names, dictionaries) for e, _ in group_by]
         self._keep += g_low
@@ -259,7 +275,7 @@ class _LoweredAggregate:
         self.garr = (Expr * max(1, len(g_low)))(*[l.c for l in g_low])
         self.gnames = (C.c_char_p * max(1, len(group_by)))(*[n.encode() for _, n in group_by])
         specs = []
-        for func, e, name in aggs:
+        for func, e, name, flt in aggs:
             s = AggSpec()
             s.func = AGG_FUNCS[func]
             s.has_arg = 0 if e is None else 1
@@ -267,6 +283,11 @@ class _LoweredAggregate:
                 l = lower(e, input_names, dictionaries)
                 self._keep.append(l)
                 s.arg = l.c
+            if flt is not None:
+                l = lower(flt, input_names, dictionaries)
+                self._keep.append(l)
+                s.has_filter = 1
+                s.filter = l.c
             s.name = name.encode()
             if return_types and name in return_types:
                 s.return_field = field_of(return_types[name])
@@ -305,7 +326,8 @@ class AggregatePlan:
 
 
 class GroupedAggregate:
-    """AggregateExec state: group_by = [(expr, name)], aggs = [(func, expr|None, name)]"""
+    """AggregateExec state: group_by = [(expr, name)], aggs = [(func, expr|None, name)] or [(func, expr|None, name, filter|None)] —
+    filter = the aggregate's FILTER (WHERE ...), a Boolean PhysicalExpr over the input (raw modes; ignored in Final modes)"""
 
     def __init__(self, mode, input_names, group_by, aggs, dictionaries: DeviceTable | None = None, return_types: dict | None = None, grouping_sets=None,
                  _lowered: "_LoweredAggregate | None" = None):
@@ -369,7 +391,7 @@ def aggregate_return_types(table: DeviceTable, aggs) -> dict:
     """declared return types of the aggregates that Final modes cannot derive from the partial state: AVG over a
     Decimal128 argument, Decimal128(min(38, p + 4), min(38, s + 4)) (functions-aggregate/src/average.rs:219-252)"""
     out = {}
-    for func, e, name in aggs:
+    for func, e, name, _ in normalize_aggs(aggs):
         if func == "avg" and e is not None:
             t = expr_type(table, e)
             if pa.types.is_decimal128(t):

@@ -465,9 +465,15 @@ def _partial_below(node: ExecutionPlan):
     return None
 
 
+def _aggr_detail(aggr_expr):
+    """the aggregates of a node's detail(): their names, a filtered one as `name FILTER (WHERE <filter>)`"""
+    return ", ".join(n if flt is None else f"{n} FILTER (WHERE {flt!r})" for _, _, n, flt in ops.normalize_aggs(aggr_expr))
+
+
 class AggregateExec(_Unary):
     """AggregateExec::try_new(mode, group_by = [(expr, name)], aggr_expr = [(func, arg | None, name)], input)
-    (aggregates/mod.rs:839)"""
+    (aggregates/mod.rs:839).  An aggregate with a FILTER (WHERE ...) is (func, arg | None, name, filter): AggregateExec::filter_expr,
+    a Boolean PhysicalExpr over the input, or None.  `aggr_expr` is kept as it was given; ops.normalize_aggs gives the 4-tuples."""
 
     def __init__(self, mode: str, group_by, aggr_expr, input: ExecutionPlan):
         self.mode, self.group_by, self.aggr_expr, self.input = mode, group_by, aggr_expr, input
@@ -491,7 +497,7 @@ class AggregateExec(_Unary):
         return out
 
     def detail(self):
-        return f"mode={self.mode}, gby=[{', '.join(n for _, n in self.group_by)}], aggr=[{', '.join(n for _, _, n in self.aggr_expr)}]"
+        return f"mode={self.mode}, gby=[{', '.join(n for _, n in self.group_by)}], aggr=[{_aggr_detail(self.aggr_expr)}]"
 
 
 class SortExec(_Unary):
@@ -566,7 +572,7 @@ class GpuFusedAggregateExec(_Unary):
         return out
 
     def detail(self):
-        return f"mode={self.mode}, predicate={self.predicate!r}, gby=[{', '.join(n for _, n in self.group_by)}], aggr=[{', '.join(n for _, _, n in self.aggr_expr)}]"
+        return f"mode={self.mode}, predicate={self.predicate!r}, gby=[{', '.join(n for _, n in self.group_by)}], aggr=[{_aggr_detail(self.aggr_expr)}]"
 
 
 class GpuHashJoinExec(HashJoinExec):
@@ -684,7 +690,9 @@ class GpuOffloadRule:
                 child = child.input
             if mapping or predicate is not None:
                 gb = [(substitute(e, mapping), n) for e, n in node.group_by]
-                aggs = [(f, None if e is None else substitute(e, mapping), n) for f, e, n in node.aggr_expr]
+                # (the projection's names are resolved inside the filters as inside the arguments; an aggregate without one keeps its 3-tuple)
+                aggs = [(f, None if e is None else substitute(e, mapping), n) if flt is None else
+                        (f, None if e is None else substitute(e, mapping), n, substitute(flt, mapping)) for f, e, n, flt in ops.normalize_aggs(node.aggr_expr)]
                 return GpuFusedAggregateExec(node.mode, gb, aggs, predicate, child)
         return node
 
@@ -760,10 +768,10 @@ def plan_schema(node):
                 raw = plan_schema(AggregateExec("Single", below.group_by, below.aggr_expr, below.input))
                 if raw is None or len(raw) != len(node.group_by) + len(node.aggr_expr):
                     return None
-                names = [n for _, n in node.group_by] + [n for _, _, n in node.aggr_expr]
+                names = [n for _, n in node.group_by] + [a[2] for a in node.aggr_expr]
                 return pa.schema([pa.field(n, f.type) for n, f in zip(names, raw)])
             fields = [pa.field(n, ops.expr_type(empty, e)) for e, n in node.group_by]
-            for func, e, n in node.aggr_expr:
+            for func, e, n, _ in ops.normalize_aggs(node.aggr_expr):   # (a FILTER changes no type: the state schema is the unfiltered one)
                 t = None if e is None else ops.expr_type(empty, e)
                 if node.mode == "Partial":      # state fields (sum.rs:281-301, average.rs:317-360, count.rs): AVG = count + sum
                     if func in ops.VARIANCE_FUNCS:   # variance.rs state_fields: count, mean, m2
@@ -831,7 +839,17 @@ def unsupported_reason(node):
         except Exception:  # noqa: BLE001
             return None
         try:
-            for func, e, n in node.aggr_expr:
+            for func, e, n, flt in ops.normalize_aggs(node.aggr_expr):
+                if flt is not None:
+                    # aggregate.hip: "the FILTER expression must be Boolean"; one the expression layer cannot lower keeps the node here too
+                    try:
+                        ft = ops.expr_type(empty, flt)
+                    except _lib.DfgpuError as err:
+                        return f"{func.upper()}({n}) FILTER (WHERE {flt!r}): {err}"
+                    except (KeyError, TypeError, ValueError) as err:
+                        return f"{func.upper()}({n}) FILTER (WHERE {flt!r}) cannot be lowered: {err}"
+                    if not pa.types.is_boolean(ft):
+                        return f"{func.upper()}({n}) FILTER (WHERE {flt!r}): the filter is {ft}, not Boolean"
                 if e is None:
                     continue
                 try:

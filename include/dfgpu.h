@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define DFGPU_ABI_VERSION 15
+#define DFGPU_ABI_VERSION 16
 
 /* Arrow C Data Interface (https://arrow.apache.org/docs/format/CDataInterface.html) */
 #ifndef ARROW_C_DATA_INTERFACE
@@ -569,7 +569,13 @@ typedef enum dfgpu_agg_mode {
  * BIT_AND .. BIT_XOR (ABI 15): bit_and_or_xor.rs — registered names bit_and, bit_or, bit_xor; the argument is Int32, Int64, UInt8,
  * UInt32 or UInt64, the result the argument's type.  BOOL_AND / BOOL_OR (ABI 15): bool_and_or.rs — bool_and, bool_or; argument and
  * result are Boolean.  NULL arguments are skipped; a group without a non-NULL value gives NULL.  Any other argument type is refused
- * ("... is not supported on the GPU path"); DISTINCT is not taken. */
+ * ("... is not supported on the GPU path"); DISTINCT and ORDER BY inside an aggregate are not taken.
+ * FILTER (ABI 16): AggregateExec::filter_expr, one optional Boolean expression per aggregate, handed to GroupsAccumulator::update_batch
+ * as opt_filter — a row reaches the aggregate only where its filter is TRUE (FALSE and NULL exclude it).  Filters never decide which
+ * groups exist: a group none of whose rows pass gives the aggregate's "nothing seen" value (NULL; 0 for COUNT).  COUNT(*) FILTER counts
+ * the rows where the filter is TRUE.  Raw modes only (Partial / Single / SinglePartitioned, grouping sets included): in Final,
+ * FinalPartitioned and PartialReduce a filter is ignored like `arg`, and the partial-state schema is that of the unfiltered aggregate.
+ * A filter that is not Boolean is an error of the first update, which names the aggregate. */
 typedef enum dfgpu_agg_func {
   DFGPU_AGG_SUM = 0, DFGPU_AGG_MIN = 1, DFGPU_AGG_MAX = 2, DFGPU_AGG_COUNT = 3, DFGPU_AGG_AVG = 4,
   DFGPU_AGG_VAR_SAMP = 5, DFGPU_AGG_VAR_POP = 6, DFGPU_AGG_STDDEV_SAMP = 7, DFGPU_AGG_STDDEV_POP = 8,
@@ -584,6 +590,8 @@ typedef struct dfgpu_agg_spec {
    * argument type.  Give it in FINAL modes for AVG(Decimal128), whose precision cannot be
    * recovered from the clamped sum-state type. */
   dfgpu_field return_field;
+  int32_t has_filter;    /* ABI 16: != 0 = FILTER (WHERE filter); a zeroed struct has none */
+  dfgpu_expr filter;     /* Boolean expression over the input (raw modes; ignored in final modes) */
 } dfgpu_agg_spec;
 
 /* AggregateExec (aggregates/mod.rs:839): group keys + accumulators

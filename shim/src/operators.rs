@@ -51,6 +51,7 @@ pub enum GpuOp {
 pub struct AggSpec {
     pub func: i32, // dfgpu_agg_func: SUM, AVG, COUNT, MIN, MAX, VAR_* / STDDEV_*, BIT_AND / BIT_OR / BIT_XOR, BOOL_AND / BOOL_OR
     pub arg: Option<Arc<Lowered>>,
+    pub filter: Option<Arc<Lowered>>, // FILTER (WHERE ...): AggregateExec::filter_expr, lowered against the node's input like `arg` (has_filter / filter)
     pub name: CString,
     pub return_field: sys::dfgpu_field,
 }
@@ -116,8 +117,9 @@ impl GpuUnaryExec {
         Some(Self { name: "GpuProjectionExec", input: Arc::clone(p.input()), op: GpuOp::Project { exprs, names }, exchange: Default::default(), cache: Arc::clone(p.properties()) })
     }
 
-    /// AggregateExec with SUM / AVG / COUNT / MIN / MAX, plain (single) grouping sets and no per-aggregate FILTER / DISTINCT /
-    /// ORDER BY (the rule leaves everything else on the CPU).  `below` = a GpuFilterExec directly under it, which is absorbed.
+    /// AggregateExec with SUM / AVG / COUNT / MIN / MAX / VAR_* / STDDEV_* / BIT_* / BOOL_*, an optional FILTER per aggregate
+    /// (dfgpu_agg_spec has_filter / filter, ABI 16) and no per-aggregate DISTINCT / ORDER BY (the rule leaves everything else on the
+    /// CPU; a filter that does not lower keeps the node there too).  `below` = a GpuFilterExec directly under it, which is absorbed.
     pub fn try_from_aggregate(a: &AggregateExec, below: Option<&GpuUnaryExec>) -> Option<Self> {
         let (input, predicate) = match below.map(|b| (&b.op, &b.input)) {
             // only an unprojected filter keeps the column numbering of the aggregate's expressions
@@ -126,7 +128,7 @@ impl GpuUnaryExec {
             _ => (Arc::clone(a.input()), None),
         };
         let in_schema = input.schema();
-        if !types_ok(&in_schema) || !types_ok(&a.schema()) || a.filter_expr().iter().any(|f| f.is_some()) {
+        if !types_ok(&in_schema) || !types_ok(&a.schema()) || a.filter_expr().len() != a.aggr_expr().len() {
             return None;
         }
         let mode = match a.mode() {
@@ -160,7 +162,7 @@ impl GpuUnaryExec {
             group_names.push(cname(name));
         }
         let mut aggs = vec![];
-        for f in a.aggr_expr() {
+        for (f, filter_expr) in a.aggr_expr().iter().zip(a.filter_expr().iter()) {
             let func = match f.fun().name().to_ascii_lowercase().as_str() {
                 "sum" => sys::DFGPU_AGG_SUM,
                 "avg" => sys::DFGPU_AGG_AVG,
@@ -216,8 +218,19 @@ impl GpuUnaryExec {
                     return None;
                 }
             }
+            // FILTER: a Boolean expression over the same input as the argument; the reference hands it to raw modes only
+            // (GroupsAccumulator::update_batch opt_filter), a state-reading mode gets none
+            let filter = match filter_expr {
+                Some(e) if raw => {
+                    if !matches!(e.data_type(&in_schema).ok(), Some(DataType::Boolean)) {
+                        return None;
+                    }
+                    Some(lowered(e, &in_schema)?)
+                }
+                _ => None,
+            };
             // Final modes cannot derive AVG(Decimal128)'s declared type from its state: AggregateFunctionExpr::return_field carries it
-            aggs.push(AggSpec { func, arg, name: cname(f.name()), return_field: field_of(f.field().data_type())? });
+            aggs.push(AggSpec { func, arg, filter, name: cname(f.name()), return_field: field_of(f.field().data_type())? });
         }
         Some(Self { name: "GpuAggregateExec", input, op: GpuOp::Aggregate { mode, group_by, group_names, aggs, predicate, grouping_sets }, exchange: Default::default(),
                     cache: Arc::clone(a.properties()) })
@@ -279,7 +292,8 @@ fn run(op: &GpuOp, input: &DeviceTable) -> Result<DeviceTable> {
             let gn: Vec<_> = group_names.iter().map(|s| s.as_ptr()).collect();
             let empty = Lowered::default();
             let specs: Vec<_> = aggs.iter().map(|a| sys::dfgpu_agg_spec { func: a.func, has_arg: a.arg.is_some() as i32, arg: a.arg.as_deref().unwrap_or(&empty).as_c(),
-                                                                         name: a.name.as_ptr(), return_field: a.return_field }).collect();
+                                                                         name: a.name.as_ptr(), return_field: a.return_field, has_filter: a.filter.is_some() as i32,
+                                                                         filter: a.filter.as_deref().unwrap_or(&empty).as_c() }).collect();
             let mut h = std::ptr::null_mut();
             match grouping_sets {
                 None => check(unsafe { sys::dfgpu_agg_create(*mode, g.as_ptr(), gn.as_ptr(), g.len() as i32, specs.as_ptr(), specs.len() as i32, &mut h) })?,
