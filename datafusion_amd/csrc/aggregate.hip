@@ -1460,7 +1460,7 @@ __global__ __launch_bounds__(BLOCK) void k_agg_fused(RowProgram p, int n_prologu
 //     added with fire-and-forget ds_add_u64 (no returned value, no dependent second atomic).  A limb cell
 //     holds < 2^43 per add and a workgroup adds < 2^20 rows, so no limb sum can wrap 64 bits; the limbs are
 //     recombined mod 2^128 at flush time — bit-identical to wrapping i128 addition in any order.
-//   * row i+stride's column loads are issued before row i is interpreted (rp_issue_row / rp_commit_row).
+//   * row i+stride's column loads are issued before row i is interpreted (rp_issue_row / tp_commit_row).
 constexpr int SM_MAX_CELLS = 48;    // LDS cells per group (an i128 sum takes 3)
 constexpr int SM_MAX_L = 256;       // local slots per workgroup
 constexpr uint64_t LIMB_MASK = (1ull << 43) - 1ull;
@@ -1526,10 +1526,10 @@ __global__ __launch_bounds__(BLOCK) void k_agg_fused_tile(TileProgram p, int pre
   const int64_t stride = (int64_t)gridDim.x * BLOCK;
   int64_t i = begin + (int64_t)blockIdx.x * BLOCK + threadIdx.x;
   RpRaw raw;
-  if (i < end) tp_issue_row(p, i, raw);
+  if (i < end) rp_issue_row(p, i, raw);
   for (; i < end; i += stride) {
     tp_commit_row(p, raw, t);
-    if (i + stride < end) tp_issue_row(p, i + stride, raw);
+    if (i + stride < end) rp_issue_row(p, i + stride, raw);
     if (pred_opnd >= 0) {
       tp_exec(p, 0, p.n_pred_end, t);
       if (!tp_true(p, t, (uint32_t)pred_opnd)) continue;

@@ -328,39 +328,51 @@ int RowProgramCompiler::keep_output_if(int out, const dfgpu_expr& filter, const 
   return out;
 }
 
-bool RowProgramCompiler::finish(CompiledProgram& cp, std::string& why) {
-  if (failed_) {
-    why = why_;
-    return false;
+static uint8_t load_kind(const dfgpu_field& f) {
+  switch (f.type) {
+    case DFGPU_INT32: case DFGPU_DATE32: return RPL_I32;
+    case DFGPU_INT64: return RPL_I64;
+    case DFGPU_UINT8: return RPL_U8;
+    case DFGPU_UINT32: return RPL_U32;
+    case DFGPU_UINT64: return RPL_U64;
+    case DFGPU_DECIMAL128: return RPL_I128;
+    case DFGPU_FLOAT64: return RPL_F64;
+    case DFGPU_BOOL: return RPL_BOOL;
   }
+  throw Error("column type " + type_name(f) + " is not supported on the GPU path");
+}
+
+// program order: literals, predicate segment, output segment (each in emission order, which is topological because operands are
+// always emitted before their users).  A value emitted in the predicate segment and reused by outputs stays live (last_use).
+RowProgramCompiler::Schedule RowProgramCompiler::schedule() const {
   const int nv = (int)vals_.size();
-  // program order: literals, predicate segment, output segment (each in emission order, which is
-  // topological because operands are always emitted before their users)
-  std::vector<int> order;
+  Schedule s;
   for (int seg = 0; seg <= 2; seg++)
     for (int v = 0; v < nv; v++)
-      if (vals_[v].seg == seg) order.push_back(v);
-  // a value first emitted in the output segment may be needed by ... nothing earlier: fine.  A value
-  // emitted in the predicate segment and reused by outputs stays live (last_use below).
-  std::vector<int> pos(nv, -1);
-  for (size_t i = 0; i < order.size(); i++) pos[order[i]] = (int)i;
-  const int n_ins = (int)order.size();
-  if (n_ins > RP_MAX_INS) {
-    why = "program needs " + std::to_string(n_ins) + " instructions";
-    return false;
-  }
-  const int INF = 1 << 30;
-  std::vector<int> last_use(nv, -1);
+      if (vals_[v].seg == seg) {
+        s.order.push_back(v);
+        if (seg == 0) s.n_prologue = (int)s.order.size();
+        if (seg <= 1) s.n_pred_end = (int)s.order.size();
+      }
+  s.n_ins = (int)s.order.size();
+  s.n_cols = (int)slot_col_.size();
+  s.pos.assign(nv, -1);
+  for (int i = 0; i < s.n_ins; i++) s.pos[s.order[i]] = i;
+  s.last_use.assign(nv, -1);
   for (int v = 0; v < nv; v++) {
     const Val& x = vals_[v];
-    if (x.op == 0xFF || x.op == RP_LIT) continue;
-    if (x.a >= 0) last_use[x.a] = std::max(last_use[x.a], pos[v]);
-    if (x.b >= 0) last_use[x.b] = std::max(last_use[x.b], pos[v]);
+    if (pinned(v)) continue;
+    if (x.a >= 0) s.last_use[x.a] = std::max(s.last_use[x.a], s.pos[v]);
+    if (x.b >= 0) s.last_use[x.b] = std::max(s.last_use[x.b], s.pos[v]);
   }
-  if (pred_ >= 0) last_use[pred_] = INF;
-  for (const RpValue& o : outs_) last_use[o.id] = INF;
-  // registers: columns own 0..n_cols-1, literals are pinned (loaded once per thread), the rest by linear scan
-  const int n_cols = (int)slot_col_.size();
+  if (pred_ >= 0) s.last_use[pred_] = Schedule::LIVE_OUT;
+  for (const RpValue& o : outs_) s.last_use[o.id] = Schedule::LIVE_OUT;
+  return s;
+}
+
+// RowProgram: columns own registers 0..n_cols-1, literals are pinned (loaded once per thread), the rest by linear scan
+bool RowProgramCompiler::emit_register_program(const Schedule& s, CompiledProgram& cp, std::string& why) const {
+  const int nv = (int)vals_.size();
   std::vector<int> reg(nv, -1);
   std::vector<bool> busy(RP_NREG, false);
   for (int v = 0; v < nv; v++)
@@ -369,27 +381,21 @@ bool RowProgramCompiler::finish(CompiledProgram& cp, std::string& why) {
       busy[reg[v]] = true;
     }
   auto alloc = [&]() -> int {
-    for (int r = n_cols; r < RP_NREG; r++)
+    for (int r = s.n_cols; r < RP_NREG; r++)
       if (!busy[r]) {
         busy[r] = true;
         return r;
       }
     return -1;
   };
-  cp = CompiledProgram{};
-  cp.n_regs = n_cols;
+  cp.n_regs = s.n_cols;
   RowProgram& P = cp.prog;
-  int n_prologue = 0, n_pred_end = 0;
-  for (int i = 0; i < n_ins; i++) {
-    const int v = order[i];
+  for (int i = 0; i < s.n_ins; i++) {
+    const int v = s.order[i];
     const Val& x = vals_[v];
-    if (x.seg == 0) n_prologue = i + 1;
-    if (x.seg <= 1) n_pred_end = i + 1;
     // operands die here unless used later; literals and columns never die
     auto release = [&](int o) {
-      if (o < 0) return;
-      if (vals_[o].op == 0xFF || vals_[o].op == RP_LIT) return;
-      if (last_use[o] == i && reg[o] >= 0) busy[reg[o]] = false;
+      if (o >= 0 && !pinned(o) && s.last_use[o] == i && reg[o] >= 0) busy[reg[o]] = false;
     };
     if (x.op != RP_LIT) {
       release(x.a);
@@ -415,230 +421,228 @@ bool RowProgramCompiler::finish(CompiledProgram& cp, std::string& why) {
       ins.aux = x.aux;
     }
     P.ins[i] = ins;
-    if (last_use[v] < 0 && last_use[v] != INF) busy[r] = false;  // dead value (cannot happen for reachable nodes)
+    if (s.last_use[v] < 0) busy[r] = false;  // dead value (cannot happen for reachable nodes)
   }
-  if (n_pred_end < n_prologue) n_pred_end = n_prologue;
-  P.n_ins = n_ins;
-  P.n_cols = n_cols;
-  for (int s = 0; s < n_cols; s++) {
-    const Column& c = in_.cols[slot_col_[s]];
-    P.col_data[s] = c.ptr();
-    P.col_valid[s] = c.valid_words();
-    int k = 0;
-    switch (c.field.type) {
-      case DFGPU_INT32: case DFGPU_DATE32: k = RPL_I32; break;
-      case DFGPU_INT64: k = RPL_I64; break;
-      case DFGPU_UINT8: k = RPL_U8; break;
-      case DFGPU_UINT32: k = RPL_U32; break;
-      case DFGPU_UINT64: k = RPL_U64; break;
-      case DFGPU_DECIMAL128: k = RPL_I128; break;
-      case DFGPU_FLOAT64: k = RPL_F64; break;
-      case DFGPU_BOOL: k = RPL_BOOL; break;
-      default: throw Error("column type " + type_name(c.field) + " is not supported on the GPU path");
-    }
-    P.col_kind[s] = (uint8_t)k;
-    cp.input_bytes_per_row += c.field.type == DFGPU_BOOL ? 1 : type_width(c.field.type);
+  P.n_ins = s.n_ins;
+  P.n_cols = s.n_cols;
+  for (int c = 0; c < s.n_cols; c++) {
+    const Column& col = in_.cols[slot_col_[c]];
+    P.col_data[c] = col.ptr();
+    P.col_valid[c] = col.valid_words();
+    P.col_kind[c] = load_kind(col.field);
+    cp.input_bytes_per_row += col.field.type == DFGPU_BOOL ? 1 : type_width(col.field.type);
   }
   for (size_t i = 0; i < lits_.size(); i++) {
     P.lit_lo[i] = lits_[i].first;
     P.lit_hi[i] = lits_[i].second;
   }
-  cp.n_prologue = n_prologue;
-  cp.n_pred_end = n_pred_end;
+  cp.n_prologue = s.n_prologue;
+  cp.n_pred_end = s.n_pred_end;
   cp.pred_reg = pred_ >= 0 ? reg[pred_] : -1;
   for (const RpValue& o : outs_) {
     cp.out_regs.push_back(reg[o.id]);
     cp.out_types.push_back(o.type);
   }
-  // ---- the same forest as a TileProgram: literals become operands, lane registers are allocated per width class
-  {
-    TileProgram& T = cp.tile;
-    T = TileProgram{};
-    std::vector<int> treg(nv, -1);      // class-local register index
-    std::vector<bool> wbusy(64, false), nbusy(64, false);
-    int n_wide = 0, n_narrow = 0;
-    auto talloc = [&](bool wide) -> int {
-      std::vector<bool>& busy_c = wide ? wbusy : nbusy;
-      for (int r2 = 0; r2 < 64; r2++)
-        if (!busy_c[r2]) {
-          busy_c[r2] = true;
-          int& hi = wide ? n_wide : n_narrow;
-          hi = std::max(hi, r2 + 1);
-          return r2;
-        }
-      return -1;
+  return true;
+}
+
+// TileProgram: literals become operands, lane registers are allocated per width class; the column and literal tables are cp.prog's
+void RowProgramCompiler::emit_tile_program(const Schedule& s, CompiledProgram& cp) const {
+  const int nv = (int)vals_.size();
+  const RowProgram& P = cp.prog;
+  TileProgram& T = cp.tile;
+  std::vector<int> treg(nv, -1);  // class-local register index
+  std::vector<bool> wbusy(64, false), nbusy(64, false);
+  int n_wide = 0, n_narrow = 0;
+  auto talloc = [&](bool wide) -> int {
+    std::vector<bool>& busy_c = wide ? wbusy : nbusy;
+    for (int r = 0; r < 64; r++)
+      if (!busy_c[r]) {
+        busy_c[r] = true;
+        int& hi = wide ? n_wide : n_narrow;
+        hi = std::max(hi, r + 1);
+        return r;
+      }
+    return -1;
+  };
+  for (int v = 0; v < nv; v++)
+    if (vals_[v].op == 0xFF) treg[v] = talloc(vals_[v].wide);
+  std::vector<int> emitted;
+  for (int i = 0; i < s.n_ins; i++) {
+    const int v = s.order[i];
+    const Val& x = vals_[v];
+    if (x.op == RP_LIT) continue;
+    auto release = [&](int o) {
+      if (o >= 0 && !pinned(o) && s.last_use[o] == i && treg[o] >= 0) (vals_[o].wide ? wbusy : nbusy)[treg[o]] = false;
     };
-    for (int v = 0; v < nv; v++)
-      if (vals_[v].op == 0xFF) treg[v] = talloc(vals_[v].wide);
-    struct Pending { int v; };
-    std::vector<Pending> emitted;
-    for (int i = 0; i < n_ins; i++) {
-      const int v = order[i];
-      const Val& x = vals_[v];
-      if (x.op == RP_LIT) continue;
-      auto release = [&](int o) {
-        if (o < 0) return;
-        if (vals_[o].op == 0xFF || vals_[o].op == RP_LIT) return;
-        if (last_use[o] == i && treg[o] >= 0) (vals_[o].wide ? wbusy : nbusy)[treg[o]] = false;
-      };
-      release(x.a);
-      if (x.b != x.a) release(x.b);
-      treg[v] = talloc(x.wide);
-      emitted.push_back({v});
-    }
-    const bool fits = n_wide + n_narrow <= 32 && (int)emitted.size() <= RP_MAX_INS;
-    if (fits) {
-      auto opnd = [&](int v) -> uint8_t {
-        if (vals_[v].op == RP_LIT) return (uint8_t)(TP_LIT | vals_[v].slot);
-        return (uint8_t)(vals_[v].wide ? treg[v] : n_wide + treg[v]);
-      };
-      T.n_ins = 0;
-      T.n_pred_end = 0;
-      for (const Pending& e : emitted) {
-        const Val& x = vals_[e.v];
-        RpIns ins{};
-        ins.op = x.op;
-        ins.dst = opnd(e.v);
-        ins.a = opnd(x.a);
-        ins.b = x.b >= 0 ? opnd(x.b) : ins.a;
-        ins.aux = x.aux;
-        T.ins[T.n_ins++] = ins;
-        if (x.seg <= 1) T.n_pred_end = T.n_ins;
-      }
-      T.n_cols = n_cols;
-      for (int v = 0; v < nv; v++)
-        if (vals_[v].op == 0xFF) T.col_reg[vals_[v].slot] = opnd(v);
-      for (int sl = 0; sl < n_cols; sl++) {
-        T.col_data[sl] = P.col_data[sl];
-        T.col_valid[sl] = P.col_valid[sl];
-        T.col_kind[sl] = P.col_kind[sl];
-      }
-      for (size_t i = 0; i < lits_.size(); i++) {
-        T.lit_lo[i] = lits_[i].first;
-        T.lit_hi[i] = lits_[i].second;
-      }
-      for (int v = 0; v < nv; v++)
-        if (vals_[v].op == RP_LIT && vals_[v].lit_null) T.lit_nulls |= 1u << vals_[v].slot;
-      T.n_wide = n_wide;
-      T.n_narrow = n_narrow;
-      cp.tile_pred = pred_ >= 0 ? opnd(pred_) : -1;
-      for (const RpValue& o : outs_) cp.tile_outs.push_back(opnd(o.id));
-    } else {
-      T.n_wide = T.n_narrow = -1;  // no tile form
-    }
+    release(x.a);
+    if (x.b != x.a) release(x.b);
+    treg[v] = talloc(x.wide);
+    emitted.push_back(v);
   }
-  // ---- the same forest as HIP source (one `const i128 V<id>` + `const bool N<id>` per value)
-  {
-    auto V = [](int v) { return "V" + std::to_string(v); };
-    auto N = [](int v) { return "N" + std::to_string(v); };
-    auto hex = [](uint64_t x) {
-      char b[32];
-      snprintf(b, sizeof b, "0x%016llxull", (unsigned long long)x);
-      return std::string(b);
-    };
-    static const char* cmp_ops[] = {"==", "!=", "<", "<=", ">", ">="};
-    auto cmp_str = [&](uint32_t aux) -> const char* {
-      switch (aux) {
-        case DFGPU_EXPR_EQ: return cmp_ops[0];
-        case DFGPU_EXPR_NE: return cmp_ops[1];
-        case DFGPU_EXPR_LT: return cmp_ops[2];
-        case DFGPU_EXPR_LE: return cmp_ops[3];
-        case DFGPU_EXPR_GT: return cmp_ops[4];
-        default: return cmp_ops[5];
-      }
-    };
-    std::string loads, pred_src, outs_src;
-    std::vector<bool> maybe_null((size_t)nv, false);
-    for (int v = 0; v < nv; v++) {
-      const Val& x = vals_[v];
-      if (x.op != 0xFF) continue;
-      maybe_null[(size_t)v] = P.col_valid[x.slot] != nullptr;
-      const std::string sl = std::to_string(x.slot), c = "C" + sl;
-      std::string decl, widen;
-      switch (P.col_kind[x.slot]) {
-        case RPL_I32: decl = "const I32 " + c + " = ((const I32*)a.col[" + sl + "])[i];"; widen = "(i128)" + c; break;
-        case RPL_U32: decl = "const U32 " + c + " = ((const U32*)a.col[" + sl + "])[i];"; widen = "(i128)" + c; break;
-        case RPL_I64: decl = "const I64 " + c + " = ((const I64*)a.col[" + sl + "])[i];"; widen = "(i128)" + c; break;
-        case RPL_U64: case RPL_F64: decl = "const U64 " + c + " = ((const U64*)a.col[" + sl + "])[i];"; widen = "(i128)(u128)" + c; break;
-        case RPL_U8: decl = "const U8 " + c + " = ((const U8*)a.col[" + sl + "])[i];"; widen = "(i128)" + c; break;
-        case RPL_I128: decl = "const i128 " + c + " = ((const i128*)a.col[" + sl + "])[i];"; widen = c; break;
-        default: decl = "const U64 " + c + " = (((const U64*)a.col[" + sl + "])[i >> 6] >> (i & 63)) & 1ull;"; widen = "(i128)" + c; break;
-      }
-      loads += "    " + decl + "\n    const i128 " + V(v) + " = " + widen + ";\n";
-      if (P.col_valid[x.slot]) loads += "    const bool " + N(v) + " = !((a.valid[" + sl + "][i >> 6] >> (i & 63)) & 1ull);\n";
-      else loads += "    const bool " + N(v) + " = false;\n";
-    }
-    for (int i = 0; i < n_ins; i++) {
-      const int v = order[i];
-      const Val& x = vals_[v];
-      std::string st;
-      const std::string A = x.a >= 0 ? V(x.a) : "", B = x.b >= 0 ? V(x.b) : A;
-      const std::string NA = x.a >= 0 ? N(x.a) : "false", NB = x.b >= 0 ? N(x.b) : NA;
-      std::string val, nul = "(" + NA + " || " + NB + ")";
-      switch (x.op) {
-        case RP_LIT:
-          val = "(i128)(((u128)" + hex(lits_[x.slot].second) + " << 64) | (u128)" + hex(lits_[x.slot].first) + ")";
-          nul = x.lit_null ? "true" : "false";
-          break;
-        case RP_ADD: val = "(i128)((u128)" + A + " + (u128)" + B + ")"; break;
-        case RP_SUB: val = "(i128)((u128)" + A + " - (u128)" + B + ")"; break;
-        case RP_MUL: val = "(i128)((u128)" + A + " * (u128)" + B + ")"; break;
-        case RP_SEXT32: val = "(i128)(I32)(U32)(U64)" + A; nul = NA; break;
-        case RP_SEXT64: val = "(i128)(I64)(U64)" + A; nul = NA; break;
-        case RP_FADD: val = "f2v(v2f(" + A + ") + v2f(" + B + "))"; break;
-        case RP_FSUB: val = "f2v(v2f(" + A + ") - v2f(" + B + "))"; break;
-        case RP_FMUL: val = "f2v(v2f(" + A + ") * v2f(" + B + "))"; break;
-        case RP_I2F: val = "f2v((double)(I64)(U64)" + A + ")"; nul = NA; break;
-        case RP_F64ORD: val = "(i128)f64ord((U64)" + A + ")"; nul = NA; break;
-        case RP_DATE_PART: val = "(i128)date32_part((I32)(U32)(U64)" + A + ", " + std::to_string(x.aux) + ")"; nul = NA; break;
-        case RP_CMP: val = "(i128)(" + A + " " + cmp_str(x.aux) + " " + B + ")"; break;
-        case RP_FCMP: val = "(i128)(f64ord((U64)" + A + ") " + cmp_str(x.aux) + " f64ord((U64)" + B + "))"; break;
-        case RP_AND:
-          val = "(i128)(kt(" + A + "," + NA + ") && kt(" + B + "," + NB + "))";
-          nul = "!((kt(" + A + "," + NA + ") && kt(" + B + "," + NB + ")) || kf(" + A + "," + NA + ") || kf(" + B + "," + NB + "))";
-          break;
-        case RP_OR:
-          val = "(i128)(kt(" + A + "," + NA + ") || kt(" + B + "," + NB + "))";
-          nul = "!(kt(" + A + "," + NA + ") || kt(" + B + "," + NB + ") || (kf(" + A + "," + NA + ") && kf(" + B + "," + NB + ")))";
-          break;
-        case RP_NOT: val = "(i128)((" + A + " & 1) ^ 1)"; nul = NA; break;
-        case RP_IS_NULL: val = "(i128)(" + NA + ")"; nul = "false"; break;
-        case RP_IS_NOT_NULL: val = "(i128)(!" + NA + ")"; nul = "false"; break;
-        case RP_GATE: val = "((" + B + " & 1) ? " + A + " : (i128)0)"; nul = "((" + B + " & 1) && " + NA + ")"; break;
-        case RP_MERGE: val = "(" + A + " | " + B + ")"; break;
-        case RP_KEEP_IF: val = A; nul = "(" + NA + " || !kt(" + B + "," + NB + "))"; break;
-        default: val = A; nul = NA; break;  // RP_MOV
-      }
-      switch (x.op) {
-        case RP_LIT: maybe_null[(size_t)v] = x.lit_null; break;
-        case RP_IS_NULL: case RP_IS_NOT_NULL: maybe_null[(size_t)v] = false; break;
-        case RP_GATE: maybe_null[(size_t)v] = maybe_null[(size_t)x.a]; break;
-        case RP_KEEP_IF: maybe_null[(size_t)v] = true; break;   // (a filtered aggregate's argument is nullable whatever its column is)
-        default: maybe_null[(size_t)v] = (x.a >= 0 && maybe_null[(size_t)x.a]) || (x.b >= 0 && maybe_null[(size_t)x.b]); break;
-      }
-      st = "    const i128 " + V(v) + " = " + val + ";\n    const bool " + N(v) + " = " + nul + ";\n";
-      if (x.seg <= 1) pred_src += st;  // literals (seg 0) are declared with the predicate: visible to both segments
-      else outs_src += st;
-    }
-    cp.src_loads = loads;
-    cp.src_pred = pred_src;
-    cp.src_outs = outs_src;
-    cp.src_pred_val = pred_;
-    cp.src_maybe_null = maybe_null;
-    for (const RpValue& o : outs_) cp.src_out_vals.push_back(o.id);
+  if (n_wide + n_narrow > 32 || (int)emitted.size() > RP_MAX_INS) {
+    T.n_wide = T.n_narrow = -1;  // no tile form
+    return;
   }
-  if (trace_on("rowprog")) {
-    static const char* names[] = {"lit", "add", "sub", "mul", "sext32", "sext64", "fadd", "fsub", "fmul", "i2f", "f64ord", "cmp", "fcmp", "and", "or", "not",
-                                  "is_null", "is_not_null", "mov", "gate", "merge", "date_part", "keep_if"};
-    fprintf(stderr, "[rowprog] cols=%d regs=%d ins=%d (prologue %d, predicate end %d, pred reg %d)\n", n_cols, cp.n_regs, n_ins, n_prologue, n_pred_end, cp.pred_reg);
-    for (int i = 0; i < n_ins; i++)
-      fprintf(stderr, "  %2d: r%-2d = %-8s r%-2d r%-2d aux=%u\n", i, P.ins[i].dst, P.ins[i].op < 23 ? names[P.ins[i].op] : "?", P.ins[i].a, P.ins[i].b, P.ins[i].aux);
-    for (size_t o = 0; o < cp.out_regs.size(); o++) fprintf(stderr, "  out%zu = r%d (%s)\n", o, cp.out_regs[o], type_name(cp.out_types[o]).c_str());
-    fprintf(stderr, "[tileprog] wide=%d narrow=%d ins=%d (predicate end %d, pred operand %d)\n", cp.tile.n_wide, cp.tile.n_narrow, cp.tile.n_ins, cp.tile.n_pred_end, cp.tile_pred);
-    for (int i = 0; i < cp.tile.n_ins; i++)
-      fprintf(stderr, "  %2d: %3d = %-8s %3d %3d aux=%u\n", i, cp.tile.ins[i].dst, cp.tile.ins[i].op < 23 ? names[cp.tile.ins[i].op] : "?", cp.tile.ins[i].a, cp.tile.ins[i].b, cp.tile.ins[i].aux);
-    for (size_t o = 0; o < cp.tile_outs.size(); o++) fprintf(stderr, "  out%zu = %d\n", o, cp.tile_outs[o]);
+  auto opnd = [&](int v) -> uint8_t {
+    if (vals_[v].op == RP_LIT) return (uint8_t)(TP_LIT | vals_[v].slot);
+    return (uint8_t)(vals_[v].wide ? treg[v] : n_wide + treg[v]);
+  };
+  for (int v : emitted) {
+    const Val& x = vals_[v];
+    RpIns ins{};
+    ins.op = x.op;
+    ins.dst = opnd(v);
+    ins.a = opnd(x.a);
+    ins.b = x.b >= 0 ? opnd(x.b) : ins.a;
+    ins.aux = x.aux;
+    T.ins[T.n_ins++] = ins;
+    if (x.seg <= 1) T.n_pred_end = T.n_ins;
   }
+  T.n_cols = s.n_cols;
+  std::copy(P.col_data, P.col_data + RP_MAX_COLS, T.col_data);
+  std::copy(P.col_valid, P.col_valid + RP_MAX_COLS, T.col_valid);
+  std::copy(P.col_kind, P.col_kind + RP_MAX_COLS, T.col_kind);
+  std::copy(P.lit_lo, P.lit_lo + RP_MAX_LITS, T.lit_lo);
+  std::copy(P.lit_hi, P.lit_hi + RP_MAX_LITS, T.lit_hi);
+  for (int v = 0; v < nv; v++) {
+    if (vals_[v].op == 0xFF) T.col_reg[vals_[v].slot] = opnd(v);
+    if (vals_[v].op == RP_LIT && vals_[v].lit_null) T.lit_nulls |= 1u << vals_[v].slot;
+  }
+  T.n_wide = n_wide;
+  T.n_narrow = n_narrow;
+  cp.tile_pred = pred_ >= 0 ? opnd(pred_) : -1;
+  for (const RpValue& o : outs_) cp.tile_outs.push_back(opnd(o.id));
+}
+
+// HIP source: one `const i128 V<id>` + `const bool N<id>` per value
+void RowProgramCompiler::emit_source(const Schedule& s, CompiledProgram& cp) const {
+  const int nv = (int)vals_.size();
+  const RowProgram& P = cp.prog;
+  auto V = [](int v) { return "V" + std::to_string(v); };
+  auto N = [](int v) { return "N" + std::to_string(v); };
+  auto hex = [](uint64_t x) {
+    char b[32];
+    snprintf(b, sizeof b, "0x%016llxull", (unsigned long long)x);
+    return std::string(b);
+  };
+  auto cmp_str = [](uint32_t aux) -> const char* {
+    switch (aux) {
+      case DFGPU_EXPR_EQ: return "==";
+      case DFGPU_EXPR_NE: return "!=";
+      case DFGPU_EXPR_LT: return "<";
+      case DFGPU_EXPR_LE: return "<=";
+      case DFGPU_EXPR_GT: return ">";
+      default: return ">=";
+    }
+  };
+  std::string loads, pred_src, outs_src;
+  std::vector<bool> maybe_null((size_t)nv, false);
+  for (int v = 0; v < nv; v++) {
+    const Val& x = vals_[v];
+    if (x.op != 0xFF) continue;
+    maybe_null[(size_t)v] = P.col_valid[x.slot] != nullptr;
+    const std::string sl = std::to_string(x.slot), c = "C" + sl;
+    std::string decl, widen;
+    switch (P.col_kind[x.slot]) {
+      case RPL_I32: decl = "const I32 " + c + " = ((const I32*)a.col[" + sl + "])[i];"; widen = "(i128)" + c; break;
+      case RPL_U32: decl = "const U32 " + c + " = ((const U32*)a.col[" + sl + "])[i];"; widen = "(i128)" + c; break;
+      case RPL_I64: decl = "const I64 " + c + " = ((const I64*)a.col[" + sl + "])[i];"; widen = "(i128)" + c; break;
+      case RPL_U64: case RPL_F64: decl = "const U64 " + c + " = ((const U64*)a.col[" + sl + "])[i];"; widen = "(i128)(u128)" + c; break;
+      case RPL_U8: decl = "const U8 " + c + " = ((const U8*)a.col[" + sl + "])[i];"; widen = "(i128)" + c; break;
+      case RPL_I128: decl = "const i128 " + c + " = ((const i128*)a.col[" + sl + "])[i];"; widen = c; break;
+      default: decl = "const U64 " + c + " = (((const U64*)a.col[" + sl + "])[i >> 6] >> (i & 63)) & 1ull;"; widen = "(i128)" + c; break;
+    }
+    loads += "    " + decl + "\n    const i128 " + V(v) + " = " + widen + ";\n";
+    if (P.col_valid[x.slot]) loads += "    const bool " + N(v) + " = !((a.valid[" + sl + "][i >> 6] >> (i & 63)) & 1ull);\n";
+    else loads += "    const bool " + N(v) + " = false;\n";
+  }
+  for (int v : s.order) {
+    const Val& x = vals_[v];
+    const std::string A = x.a >= 0 ? V(x.a) : "", B = x.b >= 0 ? V(x.b) : A;
+    const std::string NA = x.a >= 0 ? N(x.a) : "false", NB = x.b >= 0 ? N(x.b) : NA;
+    std::string val, nul = "(" + NA + " || " + NB + ")";
+    switch (x.op) {
+      case RP_LIT:
+        val = "(i128)(((u128)" + hex(lits_[x.slot].second) + " << 64) | (u128)" + hex(lits_[x.slot].first) + ")";
+        nul = x.lit_null ? "true" : "false";
+        break;
+      case RP_ADD: val = "(i128)((u128)" + A + " + (u128)" + B + ")"; break;
+      case RP_SUB: val = "(i128)((u128)" + A + " - (u128)" + B + ")"; break;
+      case RP_MUL: val = "(i128)((u128)" + A + " * (u128)" + B + ")"; break;
+      case RP_SEXT32: val = "(i128)(I32)(U32)(U64)" + A; nul = NA; break;
+      case RP_SEXT64: val = "(i128)(I64)(U64)" + A; nul = NA; break;
+      case RP_FADD: val = "f2v(v2f(" + A + ") + v2f(" + B + "))"; break;
+      case RP_FSUB: val = "f2v(v2f(" + A + ") - v2f(" + B + "))"; break;
+      case RP_FMUL: val = "f2v(v2f(" + A + ") * v2f(" + B + "))"; break;
+      case RP_I2F: val = "f2v((double)(I64)(U64)" + A + ")"; nul = NA; break;
+      case RP_F64ORD: val = "(i128)f64ord((U64)" + A + ")"; nul = NA; break;
+      case RP_DATE_PART: val = "(i128)date32_part((I32)(U32)(U64)" + A + ", " + std::to_string(x.aux) + ")"; nul = NA; break;
+      case RP_CMP: val = "(i128)(" + A + " " + cmp_str(x.aux) + " " + B + ")"; break;
+      case RP_FCMP: val = "(i128)(f64ord((U64)" + A + ") " + cmp_str(x.aux) + " f64ord((U64)" + B + "))"; break;
+      case RP_AND:
+        val = "(i128)(kt(" + A + "," + NA + ") && kt(" + B + "," + NB + "))";
+        nul = "!((kt(" + A + "," + NA + ") && kt(" + B + "," + NB + ")) || kf(" + A + "," + NA + ") || kf(" + B + "," + NB + "))";
+        break;
+      case RP_OR:
+        val = "(i128)(kt(" + A + "," + NA + ") || kt(" + B + "," + NB + "))";
+        nul = "!(kt(" + A + "," + NA + ") || kt(" + B + "," + NB + ") || (kf(" + A + "," + NA + ") && kf(" + B + "," + NB + ")))";
+        break;
+      case RP_NOT: val = "(i128)((" + A + " & 1) ^ 1)"; nul = NA; break;
+      case RP_IS_NULL: val = "(i128)(" + NA + ")"; nul = "false"; break;
+      case RP_IS_NOT_NULL: val = "(i128)(!" + NA + ")"; nul = "false"; break;
+      case RP_GATE: val = "((" + B + " & 1) ? " + A + " : (i128)0)"; nul = "((" + B + " & 1) && " + NA + ")"; break;
+      case RP_MERGE: val = "(" + A + " | " + B + ")"; break;
+      case RP_KEEP_IF: val = A; nul = "(" + NA + " || !kt(" + B + "," + NB + "))"; break;
+      default: val = A; nul = NA; break;  // RP_MOV
+    }
+    switch (x.op) {
+      case RP_LIT: maybe_null[(size_t)v] = x.lit_null; break;
+      case RP_IS_NULL: case RP_IS_NOT_NULL: maybe_null[(size_t)v] = false; break;
+      case RP_GATE: maybe_null[(size_t)v] = maybe_null[(size_t)x.a]; break;
+      case RP_KEEP_IF: maybe_null[(size_t)v] = true; break;   // (a filtered aggregate's argument is nullable whatever its column is)
+      default: maybe_null[(size_t)v] = (x.a >= 0 && maybe_null[(size_t)x.a]) || (x.b >= 0 && maybe_null[(size_t)x.b]); break;
+    }
+    const std::string st = "    const i128 " + V(v) + " = " + val + ";\n    const bool " + N(v) + " = " + nul + ";\n";
+    if (x.seg <= 1) pred_src += st;  // literals (seg 0) are declared with the predicate: visible to both segments
+    else outs_src += st;
+  }
+  cp.src_loads = loads;
+  cp.src_pred = pred_src;
+  cp.src_outs = outs_src;
+  cp.src_pred_val = pred_;
+  cp.src_maybe_null = maybe_null;
+  for (const RpValue& o : outs_) cp.src_out_vals.push_back(o.id);
+}
+
+void RowProgramCompiler::trace(const CompiledProgram& cp) const {
+  auto name = [](uint8_t op) { return op < RP_OP_COUNT ? RP_OP_NAMES[op] : "?"; };
+  const RowProgram& P = cp.prog;
+  const TileProgram& T = cp.tile;
+  fprintf(stderr, "[rowprog] cols=%d regs=%d ins=%d (prologue %d, predicate end %d, pred reg %d)\n", P.n_cols, cp.n_regs, P.n_ins, cp.n_prologue, cp.n_pred_end, cp.pred_reg);
+  for (int i = 0; i < P.n_ins; i++) fprintf(stderr, "  %2d: r%-2d = %-8s r%-2d r%-2d aux=%u\n", i, P.ins[i].dst, name(P.ins[i].op), P.ins[i].a, P.ins[i].b, P.ins[i].aux);
+  for (size_t o = 0; o < cp.out_regs.size(); o++) fprintf(stderr, "  out%zu = r%d (%s)\n", o, cp.out_regs[o], type_name(cp.out_types[o]).c_str());
+  fprintf(stderr, "[tileprog] wide=%d narrow=%d ins=%d (predicate end %d, pred operand %d)\n", T.n_wide, T.n_narrow, T.n_ins, T.n_pred_end, cp.tile_pred);
+  for (int i = 0; i < T.n_ins; i++) fprintf(stderr, "  %2d: %3d = %-8s %3d %3d aux=%u\n", i, T.ins[i].dst, name(T.ins[i].op), T.ins[i].a, T.ins[i].b, T.ins[i].aux);
+  for (size_t o = 0; o < cp.tile_outs.size(); o++) fprintf(stderr, "  out%zu = %d\n", o, cp.tile_outs[o]);
+}
+
+// one schedule, three forms of the same forest
+bool RowProgramCompiler::finish(CompiledProgram& cp, std::string& why) {
+  if (failed_) {
+    why = why_;
+    return false;
+  }
+  const Schedule s = schedule();
+  if (s.n_ins > RP_MAX_INS) {
+    why = "program needs " + std::to_string(s.n_ins) + " instructions";
+    return false;
+  }
+  cp = CompiledProgram{};
+  if (!emit_register_program(s, cp, why)) return false;
+  emit_tile_program(s, cp);
+  emit_source(s, cp);
+  if (trace_on("rowprog")) trace(cp);
   return true;
 }
 

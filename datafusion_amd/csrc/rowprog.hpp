@@ -50,6 +50,15 @@ enum RpOp : uint8_t {
   // agg(x) FILTER (WHERE p): the aggregate's argument is x where p is TRUE and NULL everywhere else (every accumulator skips NULLs)
   RP_KEEP_IF = 22    // dst <- a, NULL if a is NULL or b is not TRUE (FALSE or NULL); RP_GATE differs: it yields a non-NULL 0
 };
+constexpr int RP_OP_COUNT = RP_KEEP_IF + 1;
+// one name per RpOp, in the enum's order (the compiler's trace).  What an op computes is in rowprog_ops.inc.
+constexpr const char* RP_OP_NAMES[] = {"lit", "add", "sub", "mul", "sext32", "sext64", "fadd", "fsub", "fmul", "i2f", "f64ord", "cmp", "fcmp", "and", "or", "not",
+                                       "is_null", "is_not_null", "mov", "gate", "merge", "date_part", "keep_if"};
+static_assert(sizeof(RP_OP_NAMES) / sizeof(RP_OP_NAMES[0]) == RP_OP_COUNT, "one name per RpOp");
+// ops that read operand a only (the compiler gives them b = a)
+__host__ __device__ constexpr bool rp_is_unary(uint8_t op) {
+  return op == RP_SEXT32 || op == RP_SEXT64 || op == RP_I2F || op == RP_F64ORD || op == RP_DATE_PART || (op >= RP_NOT && op <= RP_MOV);
+}
 // how a column is widened into a register
 enum RpLoad : uint8_t { RPL_I32 = 0, RPL_I64 = 1, RPL_U8 = 2, RPL_U32 = 3, RPL_U64 = 4, RPL_I128 = 5, RPL_F64 = 6, RPL_BOOL = 7 };
 
@@ -94,9 +103,6 @@ struct RpRegs {
   RpRegs r{r##_w0, r##_w1, r##_w2, r##_w3, 0u}
 
 __device__ __forceinline__ bool rp_is_null(const RpRegs& r, int reg) { return (r.nulls >> reg) & 1u; }
-__device__ __forceinline__ void rp_set_null(RpRegs& r, int reg, bool isnull) {
-  r.nulls = (r.nulls & ~(1u << reg)) | ((isnull ? 1u : 0u) << reg);
-}
 // predicate semantics of FilterExec: NULL => row dropped (arrow-select filter)
 __device__ __forceinline__ bool rp_true(const RpRegs& r, int reg) { return !rp_is_null(r, reg) && (r.w0[reg] & 1u); }
 
@@ -135,15 +141,16 @@ __device__ __forceinline__ void rp_load_row(const RowProgram& p, int64_t row, Rp
 }
 
 // Software-pipelined variant of rp_load_row: rp_issue_row starts the loads of a (future) row into a
-// statically indexed staging set, rp_commit_row widens a completed set into the register file.  A kernel
-// issues row i+stride before interpreting row i, so HBM latency overlaps the interpreter even at the low
-// occupancy its VGPR footprint allows.
+// statically indexed staging set, tp_commit_row (below) widens a completed set into the register file.  A
+// kernel issues row i+stride before interpreting row i, so HBM latency overlaps the interpreter even at the
+// low occupancy its VGPR footprint allows.  P: any program with n_cols / col_data / col_kind / col_valid.
 struct RpRaw {
   uint64_t lo[RP_MAX_COLS];
   uint64_t hi[RP_MAX_COLS];
   uint32_t nulls;
 };
-__device__ __forceinline__ void rp_issue_row(const RowProgram& p, int64_t row, RpRaw& w) {
+template <class P>
+__device__ __forceinline__ void rp_issue_row(const P& p, int64_t row, RpRaw& w) {
   // raw loads only: anything computed from a loaded value here would put the s_waitcnt at issue time.
   // (Validity bits are the exception — a nullable column costs the wait; TPC-H columns are non-null.)
   uint32_t nulls = 0;
@@ -166,23 +173,6 @@ __device__ __forceinline__ void rp_issue_row(const RowProgram& p, int64_t row, R
     }
   }
   w.nulls = nulls;
-}
-__device__ __forceinline__ void rp_commit_row(const RowProgram& p, const RpRaw& w, RpRegs& r) {
-#pragma unroll
-  for (int c = 0; c < RP_MAX_COLS; c++) {
-    if (c < p.n_cols) {
-      uint64_t lo = w.lo[c], hi = w.hi[c];
-      switch (p.col_kind[c]) {
-        case RPL_I32: lo = (uint64_t)(int64_t)(int32_t)(uint32_t)lo; hi = (uint64_t)((int64_t)lo >> 63); break;
-        case RPL_I64: hi = (uint64_t)((int64_t)lo >> 63); break;
-        case RPL_BOOL: lo = (lo >> hi) & 1ull; hi = 0; break;
-        default: break;
-      }
-      r.set(c, lo, hi);
-    }
-  }
-  const uint32_t colmask = (1u << p.n_cols) - 1u;
-  r.nulls = (r.nulls & ~colmask) | w.nulls;
 }
 
 __device__ __forceinline__ int64_t rp_f64_ordered(uint64_t bits) {
@@ -212,38 +202,7 @@ __device__ __forceinline__ void rp_exec(const RowProgram& p, int k0, int k1, RpR
     bool on = an | bn;
     switch (in.op) {
       case RP_LIT: olo = p.lit_lo[in.aux]; ohi = p.lit_hi[in.aux]; on = in.a != 0; break;
-      case RP_ADD: { u128 v = (((u128)ahi << 64) | alo) + (((u128)bhi << 64) | blo); olo = (uint64_t)v; ohi = (uint64_t)(v >> 64); break; }
-      case RP_SUB: { u128 v = (((u128)ahi << 64) | alo) - (((u128)bhi << 64) | blo); olo = (uint64_t)v; ohi = (uint64_t)(v >> 64); break; }
-      case RP_MUL: { u128 v = (((u128)ahi << 64) | alo) * (((u128)bhi << 64) | blo); olo = (uint64_t)v; ohi = (uint64_t)(v >> 64); break; }
-      case RP_SEXT32: { int64_t s = (int64_t)(int32_t)(uint32_t)alo; olo = (uint64_t)s; ohi = (uint64_t)(s >> 63); on = an; break; }
-      case RP_SEXT64: olo = alo; ohi = (uint64_t)((int64_t)alo >> 63); on = an; break;
-      case RP_FADD: olo = (uint64_t)__double_as_longlong(__longlong_as_double((long long)alo) + __longlong_as_double((long long)blo)); break;
-      case RP_FSUB: olo = (uint64_t)__double_as_longlong(__longlong_as_double((long long)alo) - __longlong_as_double((long long)blo)); break;
-      case RP_FMUL: olo = (uint64_t)__double_as_longlong(__longlong_as_double((long long)alo) * __longlong_as_double((long long)blo)); break;
-      case RP_I2F: olo = (uint64_t)__double_as_longlong((double)(int64_t)alo); on = an; break;
-      case RP_F64ORD: { int64_t s = rp_f64_ordered(alo); olo = (uint64_t)s; ohi = (uint64_t)(s >> 63); on = an; break; }
-      case RP_DATE_PART: { int64_t s = (int64_t)date32_part((int32_t)(uint32_t)alo, (int)in.aux); olo = (uint64_t)s; ohi = (uint64_t)(s >> 63); on = an; break; }
-      case RP_CMP: olo = rp_cmp128(in.aux, (i128)(((u128)ahi << 64) | alo), (i128)(((u128)bhi << 64) | blo)) ? 1ull : 0ull; break;
-      case RP_FCMP: olo = rp_cmp128(in.aux, (i128)rp_f64_ordered(alo), (i128)rp_f64_ordered(blo)) ? 1ull : 0ull; break;
-      case RP_AND: {  // and_kleene: false AND x = false
-        bool at = !an && (alo & 1), af = !an && !(alo & 1), bt = !bn && (blo & 1), bf = !bn && !(blo & 1);
-        olo = (at && bt) ? 1ull : 0ull;
-        on = !((at && bt) || af || bf);
-        break;
-      }
-      case RP_OR: {  // or_kleene: true OR x = true
-        bool at = !an && (alo & 1), af = !an && !(alo & 1), bt = !bn && (blo & 1), bf = !bn && !(blo & 1);
-        olo = (at || bt) ? 1ull : 0ull;
-        on = !(at || bt || (af && bf));
-        break;
-      }
-      case RP_NOT: olo = (alo & 1) ^ 1ull; on = an; break;
-      case RP_IS_NULL: olo = an ? 1ull : 0ull; on = false; break;
-      case RP_IS_NOT_NULL: olo = an ? 0ull : 1ull; on = false; break;
-      case RP_GATE: { const bool t = (blo & 1) != 0; olo = t ? alo : 0ull; ohi = t ? ahi : 0ull; on = t && an; break; }
-      case RP_MERGE: olo = alo | blo; ohi = ahi | bhi; break;
-      case RP_KEEP_IF: olo = alo; ohi = ahi; on = an || bn || !(blo & 1); break;
-      default: olo = alo; ohi = ahi; on = an; break;  // RP_MOV
+#include "rowprog_ops.inc"
     }
     r.set(rd, olo, ohi);
     r.nulls = (r.nulls & ~(1u << rd)) | ((on ? 1u : 0u) << rd);
@@ -307,7 +266,7 @@ __device__ __forceinline__ void tp_store(const TileProgram& p, TileRegs& t, uint
   }
   t.nulls = (t.nulls & ~(1u << reg)) | ((isnull ? 1u : 0u) << reg);
 }
-// staged column values -> lane registers (widening as rp_commit_row)
+// staged column values (rp_issue_row) -> lane registers, widened
 __device__ __forceinline__ void tp_commit_row(const TileProgram& p, const RpRaw& w, TileRegs& t) {
 #pragma unroll
   for (int c = 0; c < RP_MAX_COLS; c++) {
@@ -323,29 +282,6 @@ __device__ __forceinline__ void tp_commit_row(const TileProgram& p, const RpRaw&
     }
   }
 }
-// issue the loads of `row` (as rp_issue_row, for a TileProgram)
-__device__ __forceinline__ void tp_issue_row(const TileProgram& p, int64_t row, RpRaw& w) {
-  uint32_t nulls = 0;
-#pragma unroll
-  for (int c = 0; c < RP_MAX_COLS; c++) {
-    if (c < p.n_cols) {
-      const void* d = p.col_data[c];
-      uint64_t lo = 0, hi = 0;
-      switch (p.col_kind[c]) {
-        case RPL_I32: case RPL_U32: lo = ((const uint32_t*)d)[row]; break;
-        case RPL_I64: case RPL_U64: case RPL_F64: lo = ((const uint64_t*)d)[row]; break;
-        case RPL_U8: lo = ((const uint8_t*)d)[row]; break;
-        case RPL_I128: { const uint64_t* q = (const uint64_t*)d + 2 * row; lo = q[0]; hi = q[1]; break; }
-        default: lo = ((const uint64_t*)d)[row >> 6]; hi = (uint64_t)(row & 63); break;  // RPL_BOOL: word + bit position
-      }
-      w.lo[c] = lo;
-      w.hi[c] = hi;
-      const uint64_t* v = p.col_valid[c];
-      if (v) nulls |= (bit_at(v, row) ? 0u : 1u) << c;
-    }
-  }
-  w.nulls = nulls;
-}
 // run instructions [k0, k1) for the current row
 __device__ __forceinline__ void tp_exec(const TileProgram& p, int k0, int k1, TileRegs& t) {
   for (int k = k0; k < k1; k++) {
@@ -353,43 +289,11 @@ __device__ __forceinline__ void tp_exec(const TileProgram& p, int k0, int k1, Ti
     uint64_t alo, ahi, blo = 0, bhi = 0;
     bool an, bn = false;
     tp_fetch(p, t, in.a, alo, ahi, an);
-    const bool unary = in.op == RP_SEXT32 || in.op == RP_SEXT64 || in.op == RP_I2F || in.op == RP_F64ORD || in.op == RP_DATE_PART || (in.op >= RP_NOT && in.op <= RP_MOV);
-    if (!unary) tp_fetch(p, t, in.b, blo, bhi, bn);
+    if (!rp_is_unary(in.op)) tp_fetch(p, t, in.b, blo, bhi, bn);
     uint64_t olo = 0, ohi = 0;
     bool on = an | bn;
     switch (in.op) {
-      case RP_ADD: { u128 v = (((u128)ahi << 64) | alo) + (((u128)bhi << 64) | blo); olo = (uint64_t)v; ohi = (uint64_t)(v >> 64); break; }
-      case RP_SUB: { u128 v = (((u128)ahi << 64) | alo) - (((u128)bhi << 64) | blo); olo = (uint64_t)v; ohi = (uint64_t)(v >> 64); break; }
-      case RP_MUL: { u128 v = (((u128)ahi << 64) | alo) * (((u128)bhi << 64) | blo); olo = (uint64_t)v; ohi = (uint64_t)(v >> 64); break; }
-      case RP_SEXT32: { int64_t s = (int64_t)(int32_t)(uint32_t)alo; olo = (uint64_t)s; ohi = (uint64_t)(s >> 63); on = an; break; }
-      case RP_SEXT64: olo = alo; ohi = (uint64_t)((int64_t)alo >> 63); on = an; break;
-      case RP_FADD: olo = (uint64_t)__double_as_longlong(__longlong_as_double((long long)alo) + __longlong_as_double((long long)blo)); break;
-      case RP_FSUB: olo = (uint64_t)__double_as_longlong(__longlong_as_double((long long)alo) - __longlong_as_double((long long)blo)); break;
-      case RP_FMUL: olo = (uint64_t)__double_as_longlong(__longlong_as_double((long long)alo) * __longlong_as_double((long long)blo)); break;
-      case RP_I2F: olo = (uint64_t)__double_as_longlong((double)(int64_t)alo); on = an; break;
-      case RP_F64ORD: { int64_t s = rp_f64_ordered(alo); olo = (uint64_t)s; ohi = (uint64_t)(s >> 63); on = an; break; }
-      case RP_DATE_PART: { int64_t s = (int64_t)date32_part((int32_t)(uint32_t)alo, (int)in.aux); olo = (uint64_t)s; ohi = (uint64_t)(s >> 63); on = an; break; }
-      case RP_CMP: olo = rp_cmp128(in.aux, (i128)(((u128)ahi << 64) | alo), (i128)(((u128)bhi << 64) | blo)) ? 1ull : 0ull; break;
-      case RP_FCMP: olo = rp_cmp128(in.aux, (i128)rp_f64_ordered(alo), (i128)rp_f64_ordered(blo)) ? 1ull : 0ull; break;
-      case RP_AND: {
-        bool at = !an && (alo & 1), af = !an && !(alo & 1), bt = !bn && (blo & 1), bf = !bn && !(blo & 1);
-        olo = (at && bt) ? 1ull : 0ull;
-        on = !((at && bt) || af || bf);
-        break;
-      }
-      case RP_OR: {
-        bool at = !an && (alo & 1), af = !an && !(alo & 1), bt = !bn && (blo & 1), bf = !bn && !(blo & 1);
-        olo = (at || bt) ? 1ull : 0ull;
-        on = !(at || bt || (af && bf));
-        break;
-      }
-      case RP_NOT: olo = (alo & 1) ^ 1ull; on = an; break;
-      case RP_IS_NULL: olo = an ? 1ull : 0ull; on = false; break;
-      case RP_IS_NOT_NULL: olo = an ? 0ull : 1ull; on = false; break;
-      case RP_GATE: { const bool g = (blo & 1) != 0; olo = g ? alo : 0ull; ohi = g ? ahi : 0ull; on = g && an; break; }
-      case RP_MERGE: olo = alo | blo; ohi = ahi | bhi; break;
-      case RP_KEEP_IF: olo = alo; ohi = ahi; on = an || bn || !(blo & 1); break;
-      default: olo = alo; ohi = ahi; on = an; break;  // RP_MOV
+#include "rowprog_ops.inc"
     }
     tp_store(p, t, in.dst, olo, ohi, on);
   }

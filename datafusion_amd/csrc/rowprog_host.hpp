@@ -95,6 +95,21 @@ class RowProgramCompiler {
     if (!failed_) why_ = why;
     failed_ = true;
   }
+  // finish(): one schedule, then the forest in its three forms (rowprog.hip)
+  struct Schedule {
+    static constexpr int LIVE_OUT = 1 << 30;  // last_use of the predicate and of every output
+    std::vector<int> order;      // value ids in program order: literals, predicate segment, output segment
+    std::vector<int> pos;        // value id -> index in `order` (-1: an input column)
+    std::vector<int> last_use;   // value id -> index of the last instruction reading it, -1 = none
+    int n_ins = 0, n_cols = 0;
+    int n_prologue = 0, n_pred_end = 0;  // segment ends: [0, n_prologue) literals, [n_prologue, n_pred_end) predicate
+  };
+  bool pinned(int v) const { return vals_[v].op == 0xFF || vals_[v].op == RP_LIT; }  // input columns and literals hold their register
+  Schedule schedule() const;
+  bool emit_register_program(const Schedule& s, CompiledProgram& cp, std::string& why) const;
+  void emit_tile_program(const Schedule& s, CompiledProgram& cp) const;
+  void emit_source(const Schedule& s, CompiledProgram& cp) const;
+  void trace(const CompiledProgram& cp) const;
 };
 
 // the text every generated source opens with: the names the source emitted by RowProgramCompiler::finish uses (rowprog.hip)

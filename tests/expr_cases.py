@@ -1,5 +1,5 @@
 """The tables and expressions of the expression-value tests, shared by tests/test_expr_reference.py (reference against the oracle, on
-the CPU) and tests/test_gpu_expr_edges.py (the three evaluators against the reference).
+the CPU) and tests/test_gpu_expr_edges.py (every evaluator against the reference).
 
 A family is one table of N = 4097 rows (64-row validity words, the 256-thread block, k_cmp's four-word unroll and a ragged tail) and
 the expressions evaluated over it.  The first rows of a table hold the full cross product of the edge values of its first two

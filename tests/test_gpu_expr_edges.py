@@ -1,13 +1,18 @@
-"""Values of `+ - * / %`, CAST, comparisons and date_part at the edges of their types, from each of the three evaluators, against the
+"""Values of `+ - * / %`, CAST, comparisons and date_part at the edges of their types, from each of the four evaluators, against the
 exact reference tests/expr_ref.py (itself held to the oracle and to Python's calendar by tests/test_expr_reference.py): bit for bit,
 a computed NaN as "is NaN", an error by its message prefix.  No tolerance appears in this file.
 
 The evaluators, each proven to have run: column-at-a-time (`ops.project`, `ops.filter`, and `ops.aggregate` with fusion off:
-fused_updates == 0), the register / tile program (jit = 0: fused_updates > 0) and the source specialised with hiprtc (jit = 1:
-fused_updates > 0 and one more node compiled; the on-disk code-object cache is off here so that a warm cache cannot serve the node
-and leave that count where it was).  A value leaves a fused node through GROUP BY row (one row per group): MAX(expr) carries an Int32 /
-Int64 / Float64 by its bits, SUM(expr) a Decimal128 by its 128-bit word (a one-row wrapping sum is the value), COUNT(expr) its
-NULL-ness.  Predicates are read both as values (tests.expr_cases.truth) and as the node's predicate, by the rows that come back.
+fused_updates == 0), the register program (`register`: jit = 0 under GROUP BY row, an Int64 key whose groups are interned by hashing,
+which is k_agg_fused with the register file in VGPRs: fused_updates > 0, nothing compiled), the tile program (`tile`: jit = 0 under
+GROUP BY two UInt8 columns, which is k_agg_fused_tile with the register file in LDS: fused_updates > 0, nothing compiled, and
+"agg_fused_tile" in the profile) and the source specialised with hiprtc (`specialised`: jit = 1: fused_updates > 0 and one more node
+compiled; the on-disk code-object cache is off here so that a warm cache cannot serve the node and leave that count where it was).
+A value leaves a fused node with one row per group: MAX(expr) carries an Int32 / Int64 / Float64 by its bits, SUM(expr) a Decimal128
+by its 128-bit word (a one-row wrapping sum is the value), COUNT(expr) its NULL-ness.  The groups are the rows: GROUP BY row, and for
+`tile` GROUP BY k0 = row & 0xFF, k1 = row >> 8 (4097 one-row groups: past the kernel's 256 local slots, into its key-indexed partials).
+Predicates are read both as values (tests.expr_cases.truth) and as the node's predicate, by the rows that come back.  date_part as
+the group key is not a `tile` case: that node's keys are plain UInt8 columns.
 
 Division and the casts the row programs decline (Decimal128 scale-down, Decimal128 <-> Float64) are column-at-a-time by design: a fused
 node holding one must fall back (fused_updates == 0) with the same values."""
@@ -24,7 +29,11 @@ from tests import expr_ref as R
 pytestmark = pytest.mark.gpu
 
 EVALUATORS = ("column", "register", "specialised")
+NODE_EVALUATORS = EVALUATORS + ("tile",)
 MAX_AGGS = 16               # accumulators of one aggregate node (csrc/aggregate.hip)
+# what one tile node holds (csrc/aggregate.hip agg_update_small_single_pass): SM_MAX_CELLS LDS cells per group, a SUM(Decimal128) taking
+# 3; and per lane (TILE_LDS_BUDGET - 4096) / BLOCK = 240 bytes of LDS register file, a Decimal128 / UInt64 register taking 16, any other 8
+TILE_CELLS, TILE_REGFILE = 48, 240
 SPECIALISED = dict(jit="1", jit__min_rows="0", jit__strict="1", jit__cache="0")
 _compiled_nodes = set()     # (family, what) whose specialised node this process has built already
 
@@ -43,12 +52,22 @@ def _aggregate(table, group_by, aggs, evaluator, predicate=None, fused=True, nod
             ops.set_fusion(False)
         else:
             ops.set_options(**(SPECIALISED if evaluator == "specialised" else dict(jit="0")))
+        if evaluator == "tile":
+            ops.profile_enable(True)
+            ops.profile_reset()
         before = ops.jit_stats()[0]
         out = ops.aggregate(_dev(table), group_by, aggs, "Single", predicate=predicate, info=info).to_arrow()
         compiled = ops.jit_stats()[0] - before
+        stats = ops.profile_stats() if evaluator == "tile" else {}
     finally:
+        if evaluator == "tile":
+            ops.profile_enable(False)
         ops.reset_options()
         ops.set_fusion(True)
+    if evaluator == "tile":
+        assert "agg_fused_tile" in stats, (sorted(stats), info)
+        assert info["fused_updates"] > 0 and compiled == 0, (info, compiled)
+        return out
     if evaluator == "column" or not fused:
         assert info["fused_updates"] == 0, (evaluator, info)
         assert compiled == 0
@@ -64,6 +83,56 @@ def _aggregate(table, group_by, aggs, evaluator, predicate=None, fused=True, nod
 
 def _by_row(out: pa.Table) -> pa.Table:
     return out.take(pa.array(np.argsort(np.asarray(out.column("row"), dtype=np.int64), kind="stable")))
+
+
+KEY_BYTES = ("k0", "k1")
+
+
+def _with_key_bytes(table: pa.Table) -> pa.Table:
+    """the table with its row number as two plain UInt8 columns: the keys of a tile node"""
+    rows = np.arange(table.num_rows)
+    return table.append_column("k0", pa.array((rows & 0xFF).astype(np.uint8))).append_column("k1", pa.array((rows >> 8).astype(np.uint8)))
+
+
+def _by_key_bytes(out: pa.Table) -> pa.Table:
+    """the groups of a tile node in row order, with the row rebuilt from (k1, k0)"""
+    rows = np.asarray(out.column("k1"), dtype=np.int64) * 256 + np.asarray(out.column("k0"), dtype=np.int64)
+    return out.append_column("row", pa.array(rows)).take(pa.array(np.argsort(rows, kind="stable")))
+
+
+def _is_wide(typ):
+    return pa.types.is_decimal128(typ) or typ == pa.uint64()
+
+
+def _tile_nodes(f, ref) -> list:
+    """the family's value names split over as few tile nodes as hold them, each value with its COUNT beside it.  A node is filled while
+    (a) its accumulators stay within MAX_AGGS, (b) its cells within TILE_CELLS, (c) its lane registers within TILE_REGFILE: the table's
+    columns and the two keys, 16 bytes per value (a Decimal128; or a Float64 with the ordered key MAX takes beside it), and 64 bytes for
+    the temporaries of one expression (two wide, four narrow: the deepest are `nest` and `truth`)."""
+    fixed = sum(16 if _is_wide(c.type) else 8 for c in f.table.drop_columns(["row"]).schema) + 2 * 8 + 64
+    nodes, accs, cells, regs = [[]], 0, 0, fixed
+    for nm, _ in f.values:
+        c = (3 if pa.types.is_decimal128(ref[nm].typ) else 1) + 1
+        if accs + 2 > MAX_AGGS or cells + c > TILE_CELLS or regs + 16 > TILE_REGFILE:
+            nodes.append([])
+            accs, cells, regs = 0, 0, fixed
+        nodes[-1].append(nm)
+        accs, cells, regs = accs + 2, cells + c, regs + 16
+    assert all(nodes) and sorted(nm for node in nodes for nm in node) == sorted(nm for nm, _ in f.values)
+    return nodes
+
+
+def _values_through_tile_nodes(f, ref):
+    """every value expression of the family through k_agg_fused_tile, GROUP BY (k0, k1)"""
+    from datafusion_amd.expr import col
+    table, exprs = _with_key_bytes(f.table), dict(f.values)
+    for names in _tile_nodes(f, ref):
+        aggs = [(_carrier(ref[nm].typ), exprs[nm], nm) for nm in names] + [("count", exprs[nm], nm + "__n") for nm in names]
+        out = _by_key_bytes(_aggregate(table, [(col(k), k) for k in KEY_BYTES], aggs, "tile"))
+        assert out.column("row").to_pylist() == list(range(table.num_rows))
+        for nm in names:
+            _check(out.column(nm), ref[nm], f"{f.name}.{nm} [tile]", carried=True)
+            assert out.column(nm + "__n").to_pylist() == [0 if v is None else 1 for v in ref[nm].vals], f"{f.name}.{nm} [tile]: COUNT"
 
 
 def _carrier(typ):
@@ -83,6 +152,8 @@ def _values_through_a_node(f, evaluator, table=None, ref=None):
     """every value expression of the family as one aggregate node, GROUP BY row"""
     from datafusion_amd.expr import col
     table, ref = f.table if table is None else table, C.reference(f.name) if ref is None else ref
+    if evaluator == "tile":
+        return _values_through_tile_nodes(f, ref)
     assert len(f.values) < MAX_AGGS
     counted = [nm for nm, _ in f.values][:MAX_AGGS - len(f.values)]          # COUNT(expr) beside as many values as the node has room for
     aggs = [(_carrier(ref[nm].typ), e, nm) for nm, e in f.values] + [("count", e, nm + "__n") for nm, e in f.values if nm in counted]
@@ -100,13 +171,16 @@ def _rows_under_the_node_predicate(f, evaluator):
     nm, pred = f.node_pred
     want = [i for i, v in enumerate(C.reference(f.name)[nm].vals) if v is True]
     assert 0 < len(want) < f.table.num_rows
-    out = _by_row(_aggregate(f.table, [(col("row"), "row")], [("count", None, "n")], evaluator, predicate=pred, node=(f.name, "predicate")))
+    if evaluator == "tile":
+        out = _by_key_bytes(_aggregate(_with_key_bytes(f.table), [(col(k), k) for k in KEY_BYTES], [("count", None, "n")], evaluator, predicate=pred))
+    else:
+        out = _by_row(_aggregate(f.table, [(col("row"), "row")], [("count", None, "n")], evaluator, predicate=pred, node=(f.name, "predicate")))
     assert out.column("row").to_pylist() == want, f"{f.name}.{nm} [{evaluator}]: rows under the node's predicate"
     assert out.column("n").to_pylist() == [1] * len(want)
 
 
 # ------------------------------------------------------------------------------------------------------------- the fused families
-@pytest.mark.parametrize("evaluator", EVALUATORS)
+@pytest.mark.parametrize("evaluator", NODE_EVALUATORS)
 @pytest.mark.parametrize("name", C.FUSED)
 def test_values_and_predicates(name, evaluator):
     from datafusion_amd import ops
