@@ -62,6 +62,11 @@ class AggSpec(C.Structure):
                 ("has_filter", C.c_int32), ("filter", Expr)]   # ABI 16: FILTER (WHERE ...); a zeroed struct has none
 
 
+class WindowSpec(C.Structure):
+    """dfgpu_window_spec (ABI 17)"""
+    _fields_ = [("func", C.c_int32), ("has_arg", C.c_int32), ("arg", Expr), ("frame", C.c_int32), ("name", C.c_char_p)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 64), ("calls", C.c_int64), ("total_ms", C.c_double),
                 ("algorithmic_bytes", C.c_int64)]
@@ -110,7 +115,7 @@ SYMBOLS = [
     "dfgpu_table_select", "dfgpu_table_hstack", "dfgpu_table_concat", "dfgpu_table_slice", "dfgpu_expr_type",
     "dfgpu_filter", "dfgpu_project", "dfgpu_join_build", "dfgpu_join_probe", "dfgpu_join_probe_filtered", "dfgpu_join_probe_with_filter", "dfgpu_column_minmax", "dfgpu_join_emit_unmatched",
     "dfgpu_join_get_info", "dfgpu_join_free", "dfgpu_agg_create", "dfgpu_agg_update", "dfgpu_agg_update_filtered", "dfgpu_agg_fused_updates", "dfgpu_set_fusion", "dfgpu_jit_stats", "dfgpu_agg_emit",
-    "dfgpu_agg_free", "dfgpu_sort", "dfgpu_partition", "dfgpu_hash_columns", "dfgpu_tpch_orders",
+    "dfgpu_agg_free", "dfgpu_sort", "dfgpu_window", "dfgpu_partition", "dfgpu_hash_columns", "dfgpu_tpch_orders",
     "dfgpu_tpch_lineitem", "dfgpu_tpch_customer", "dfgpu_profile_enable", "dfgpu_profile_reset",
     "dfgpu_profile_count", "dfgpu_profile_get", "dfgpu_profile_launches", "dfgpu_join_probe_bounded", "dfgpu_parquet_decode_chunk", "dfgpu_parquet_inspect_chunk", "dfgpu_parquet_read_chunks",
     "dfgpu_comm_unique_id", "dfgpu_comm_init_rank", "dfgpu_comm_init_all", "dfgpu_comm_init_host", "dfgpu_comm_free", "dfgpu_comm_info", "dfgpu_comm_transport_info",

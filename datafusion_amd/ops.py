@@ -8,7 +8,7 @@ import ctypes as C
 import pyarrow as pa
 
 from . import _lib
-from ._lib import AggSpec, Expr, Field, JoinFilter, JoinInfo, JoinOptions, KernelStat, check
+from ._lib import AggSpec, Expr, Field, JoinFilter, JoinInfo, JoinOptions, KernelStat, WindowSpec, check
 from .expr import LoweredExpr, PhysicalExpr, lower
 from .table import DeviceTable, field_of
 
@@ -26,6 +26,12 @@ BITWISE_FUNCS = frozenset(("bit_and", "bit_or", "bit_xor"))
 BOOLEAN_FUNCS = frozenset(("bool_and", "bool_or"))
 GPU_MIN_KEY_DENSITY = 1.0 / 64.0      # DFGPU_DEFAULT_MIN_KEY_DENSITY (include/dfgpu.h); the reference's CPU default is 0.15
 TABLE_MODES = {"auto": 0, "hash_map": 1, "array_map": 2, "rank_map": 3}
+# dfgpu_window_func / dfgpu_window_frame (include/dfgpu.h); WINDOW_TILE = DFGPU_WINDOW_TILE, the rows one workgroup of the window's
+# segmented scan takes (tests/test_window_abi.py holds it to the header)
+WINDOW_FUNCS = {"row_number": 0, "rank": 1, "dense_rank": 2, "sum": 3, "count": 4, "min": 5, "max": 6, "avg": 7}
+WINDOW_RANKING = frozenset(("row_number", "rank", "dense_rank"))
+WINDOW_FRAMES = {"range_to_current": 0, "rows_to_current": 1, "partition": 2}
+WINDOW_TILE = 2048
 PROBE_MODES = {"auto": 0, "two_pass": 1, "single_pass_ordered": 2, "single_pass_unordered": 3, "order_not_needed": 4}
 
 
@@ -236,6 +242,50 @@ def sort(table: DeviceTable, keys, fetch=None) -> DeviceTable:
     nf = (C.c_uint8 * len(keys))(*[int(f) for _, _, f in keys])
     out = C.c_void_p()
     check(lib.dfgpu_sort(table.handle, _ints(idx), desc, nf, len(keys), C.c_int64(-1 if fetch is None else fetch), C.byref(out)))
+    return DeviceTable(out)
+
+
+def normalize_window_exprs(exprs):
+    """a window expression is (func, arg | None, name, frame); frame None (or left out) = range_to_current, the default under an ORDER BY"""
+    out = []
+    for w in exprs or []:
+        if len(w) == 3:
+            w = tuple(w) + (None,)
+        if len(w) != 4:
+            raise ValueError(f"a window expression is (func, arg | None, name, frame), not {w!r}")
+        func, arg, name, frame = w
+        frame = "range_to_current" if frame is None else frame
+        if func not in WINDOW_FUNCS:
+            raise ValueError(f"window function {func!r} is not supported on the GPU path")
+        if frame not in WINDOW_FRAMES:
+            raise ValueError(f"window frame {frame!r} is not supported on the GPU path")
+        out.append((func, None if func in WINDOW_RANKING else arg, name, frame))
+    return out
+
+
+def window(table: DeviceTable, partition_by, order_by, exprs) -> DeviceTable:
+    """WindowAggExec / BoundedWindowAggExec over a table already ordered by (partition_by, order_by) — column names or indices; exprs =
+    [(func, arg | None, name, frame)], func in WINDOW_FUNCS, frame in WINDOW_FRAMES.  The result is the input's columns (the same
+    buffers) followed by one column per expression."""
+    lib = _lib.init()
+    names = table.column_names
+    pidx = [table.index_of(c) for c in partition_by or []]
+    oidx = [table.index_of(c) for c in order_by or []]
+    keep, specs = [], []
+    for func, arg, name, frame in normalize_window_exprs(exprs):
+        s = WindowSpec()
+        s.func = WINDOW_FUNCS[func]
+        s.has_arg = 0 if arg is None else 1
+        if arg is not None:
+            l = lower(arg, names, table)
+            keep.append(l)
+            s.arg = l.c
+        s.frame = WINDOW_FRAMES[frame]
+        s.name = name.encode()
+        specs.append(s)
+    sarr = (WindowSpec * max(1, len(specs)))(*specs)
+    out = C.c_void_p()
+    check(lib.dfgpu_window(table.handle, _ints(pidx), len(pidx), _ints(oidx), len(oidx), sarr, len(specs), C.byref(out)))
     return DeviceTable(out)
 
 

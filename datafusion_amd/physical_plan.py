@@ -17,6 +17,7 @@ per-operator GPU node):
   CoalesceBatchesExec / CoalescePartitionsExec       -> removed                 (whole partitions per launch)
   RepartitionExec(Hash) on one GPU                   -> removed                 (one partition per GPU)
   SortPreservingMergeExec on one GPU                 -> removed                 (one sorted partition is the merge)
+WindowAggExec stays the node it is (dfgpu_window); the rule demands order of its child, so the SortExec below keeps its meaning.
 """
 from __future__ import annotations
 
@@ -521,6 +522,37 @@ class SortExec(_Unary):
         return ("TopK(fetch=%d), " % self.fetch if self.fetch is not None else "") + str([(c, "DESC" if d else "ASC") for c, d, _ in self.expr])
 
 
+class WindowAggExec(_Unary):
+    """WindowAggExec / BoundedWindowAggExec (physical-plan/src/windows/): window_expr = [(func, arg | None, name, frame)] — func one of
+    ops.WINDOW_FUNCS, frame one of ops.WINDOW_FRAMES (None = range_to_current, the default under an ORDER BY) — over
+    PARTITION BY partition_by ORDER BY order_by.  partition_by = columns; order_by = columns or (column, descending, nulls_first) as
+    SortExec takes them: direction and NULL placement are kept for display only, the operator looks at equality of neighbouring rows.
+    The input must arrive ordered by (partition_by, order_by) — the SortExec the planner puts below; the two reference nodes differ
+    in streaming, not in results, and this node is both."""
+
+    def __init__(self, window_expr, partition_by, order_by, input: ExecutionPlan):
+        self.window_expr, self.partition_by, self.input = window_expr, list(partition_by or []), input
+        self.order_by = [o if isinstance(o, tuple) else (o, False, False) for o in (order_by or [])]
+
+    def with_new_children(self, c):
+        return WindowAggExec(self.window_expr, self.partition_by, self.order_by, c[0])
+
+    def execute(self, partition=0):
+        t, owned = self._run_child(self.input)
+        out = ops.window(t, self.partition_by, [c for c, _, _ in self.order_by], self.window_expr)
+        if owned:
+            t.free()      # (the output's input columns hold their buffers themselves)
+        return out
+
+    def detail(self):
+        def one(func, arg, name, frame):
+            over = "" if func in ops.WINDOW_RANKING else f" {frame}"
+            return f"{func}({'' if arg is None else repr(arg)}){over} AS {name}"
+        order = ", ".join(f"{c} {'DESC' if d else 'ASC'} NULLS {'FIRST' if nf else 'LAST'}" for c, d, nf in self.order_by)
+        return (f"wdw=[{', '.join(one(*w) for w in ops.normalize_window_exprs(self.window_expr))}], "
+                f"partition_by=[{', '.join(str(c) for c in self.partition_by)}], order_by=[{order}]")
+
+
 # ------------------------------------------------------------------------------ fused GPU nodes
 class ScalarSubqueryExec(ExecutionPlan):
     """physical-plan/src/scalar_subquery.rs:85 — a pass-through over its main input that first runs every (uncorrelated) scalar
@@ -644,6 +676,8 @@ class GpuOffloadRule:
         for i, c in enumerate(node.children()):
             if isinstance(node, (AggregateExec, GpuFusedAggregateExec, RepartitionExec, SortExec)):
                 need = False                                   # these consume their input in any order
+            elif isinstance(node, WindowAggExec):
+                need = True                                    # partitions and peer groups ARE the input's order, whatever the parent needs
             elif isinstance(node, HashJoinExec):
                 need = parent_needs_order and i == 1           # only the probe side's order shows in the output
             else:
@@ -656,6 +690,11 @@ class GpuOffloadRule:
             return node.input
         if isinstance(node, (RepartitionExec, CoalescePartitionsExec, SortPreservingMergeExec)) and self.world_size == 1:
             return node.input                                  # one partition: nothing to exchange, gather or merge
+        if isinstance(node, WindowAggExec) and self.world_size > 1 and not getattr(node, "kept_on_cpu", False):
+            # a window over several ranks needs its partitions co-located first; that path is not exercised, so the node is not taken
+            node.kept_on_cpu = True
+            self.declined.append((node, f"WindowAggExec on {self.world_size} ranks: the window is only exercised on one rank"))
+            return node
         if not isinstance(node, (GpuHashJoinExec, GpuFusedAggregateExec)) and not getattr(node, "kept_on_cpu", False):
             try:
                 reason = unsupported_reason(node)
@@ -705,6 +744,9 @@ def _row_bound(node):
     if isinstance(node, (FilterExec, ProjectionExec, CoalesceBatchesExec, RepartitionExec, CoalescePartitionsExec, SortExec, SortPreservingMergeExec,
                          AggregateExec, GpuFusedAggregateExec)):
         return _row_bound(node.children()[0])
+    if isinstance(node, WindowAggExec):   # every input row, 16 bytes more per window column at the most (a Decimal128 result)
+        rows, width = _row_bound(node.input)
+        return rows, width + 16 * len(node.window_expr)
     if isinstance(node, HashJoinExec):
         (br, bb), (pr, pb) = _row_bound(node.left), _row_bound(node.right)
         return max(br, pr), bb + pb
@@ -757,6 +799,14 @@ def plan_schema(node):
     except Exception:  # noqa: BLE001 - no device (planning-only tests): nothing can be typed
         return None
     try:
+        if isinstance(node, WindowAggExec):
+            fields = list(inp)
+            for func, e, n, _ in ops.normalize_window_exprs(node.window_expr):
+                if func in ops.WINDOW_RANKING:
+                    fields.append(pa.field(n, pa.uint64(), nullable=False))
+                else:
+                    fields.append(pa.field(n, _agg_type(func, None if e is None else ops.expr_type(empty, e)), nullable=func != "count"))
+            return pa.schema(fields)
         if isinstance(node, ProjectionExec):
             return pa.schema([pa.field(n, ops.expr_type(empty, e)) for e, n in node.exprs])
         if isinstance(node, (AggregateExec, GpuFusedAggregateExec)):
@@ -877,6 +927,47 @@ def unsupported_reason(node):
                     return f"{func.upper()}({n}) over {t} is not supported on the GPU path"
                 if func in ops.BOOLEAN_FUNCS and not pa.types.is_boolean(t):
                     # aggregate.hip plan_for: BOOL_AND / BOOL_OR take a Boolean
+                    return f"{func.upper()}({n}) over {t} is not supported on the GPU path"
+        finally:
+            empty.free()
+        return None
+    if isinstance(node, WindowAggExec):
+        inp = plan_schema(node.input)
+        if inp is None:
+            return None
+        for c in node.partition_by + [c for c, _, _ in node.order_by]:
+            t = inp.field(inp.get_field_index(c) if isinstance(c, str) else c).type
+            # window.hip window_keys: keys are compared by value bits plus validity.  How the reference treats +0.0 / -0.0 and NaN as
+            # peers cannot be checked here, so Float64 keys are not taken; Boolean keys are bit-packed, Utf8 keys have no fixed width
+            if pa.types.is_floating(t):
+                return "Float64 window keys are not supported on the GPU path"
+            if pa.types.is_boolean(t):
+                return "Boolean window keys are not supported on the GPU path"
+            if pa.types.is_string(t) or pa.types.is_large_string(t):
+                return "Utf8 window keys are not supported on the GPU path"
+        try:
+            empty = DeviceTable.from_arrow(inp.empty_table())
+        except Exception:  # noqa: BLE001
+            return None
+        try:
+            for func, e, n, _ in ops.normalize_window_exprs(node.window_expr):
+                if e is None or func == "count":
+                    continue
+                try:
+                    t = ops.expr_type(empty, e)
+                except _lib.DfgpuError as err:
+                    return f"{func}({e!r}): {err}"
+                except (KeyError, TypeError, ValueError):
+                    continue
+                if func == "avg" and pa.types.is_decimal128(t) and t.precision + 13 > 38:
+                    # window.hip plan_window: the aggregate's refusal (avg_sum_data_type widens to Decimal256 beyond 38 digits)
+                    return f"AVG({n}) over {t} accumulates in Decimal256 in the reference (no device representation)"
+                # window.hip plan_window: the argument types of the GPU AggregateExec (MIN / MAX over Decimal128 at any precision)
+                ok = {"sum": (pa.int32(), pa.int64(), pa.uint8(), pa.uint32(), pa.uint64(), pa.float64()),
+                      "avg": (pa.int32(), pa.int64(), pa.float64()),
+                      "min": (pa.int32(), pa.int64(), pa.uint8(), pa.uint32(), pa.float64(), pa.date32()),
+                      "max": (pa.int32(), pa.int64(), pa.uint8(), pa.uint32(), pa.float64(), pa.date32())}[func]
+                if not (pa.types.is_decimal128(t) or t in ok):
                     return f"{func.upper()}({n}) over {t} is not supported on the GPU path"
         finally:
             empty.free()

@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define DFGPU_ABI_VERSION 16
+#define DFGPU_ABI_VERSION 17
 
 /* Arrow C Data Interface (https://arrow.apache.org/docs/format/CDataInterface.html) */
 #ifndef ARROW_C_DATA_INTERFACE
@@ -668,6 +668,51 @@ int dfgpu_agg_free(dfgpu_agg_t h);
  * (topk/mod.rs:397) when fetch >= 0. */
 int dfgpu_sort(dfgpu_table_t input, const int* key_cols, const uint8_t* descending, const uint8_t* nulls_first,
                int nkeys, int64_t fetch, dfgpu_table_t* out);
+
+/* WindowAggExec / BoundedWindowAggExec (ABI 17; physical-plan/src/windows/): ranking functions and running aggregates
+ * `... OVER (PARTITION BY p ORDER BY o)` over input that is ALREADY ordered by (p, o) — the SortExec the planner puts below the
+ * node; the order is trusted, as the reference's node trusts it.  The two reference nodes differ in streaming, not in results: this
+ * entry point is both.
+ *   partition  = a maximal run of adjacent rows whose partition columns are all equal (NULL equals NULL); no partition columns:
+ *                the whole input
+ *   peer group = a maximal run of adjacent rows of one partition whose order columns are all equal (NULL equals NULL); no order
+ *                columns: every row of a partition is a peer of every other
+ * Only equality of neighbouring rows matters: sort direction and NULL placement change no result and are not passed.
+ * Key columns (partition and order) are Int32, Int64, UInt8, UInt32, UInt64, Date32, Decimal128 or dictionary-encoded strings and
+ * are compared by value bits plus validity; Float64, Boolean and Utf8 keys are refused ("... window keys are not supported on the
+ * GPU path"); at most 8 partition and 8 order columns.
+ * ROW_NUMBER = 1-based position in the partition, RANK = position of the first row of the peer group, DENSE_RANK = peer groups of
+ * the partition up to and including the row's own: UInt64, never NULL, `arg` and `frame` ignored.
+ * SUM / COUNT / MIN / MAX / AVG run over a frame that starts at the partition's first row and ends at the current row
+ * (ROWS_TO_CURRENT), at the last peer of the current row (RANGE_TO_CURRENT: the default frame under an ORDER BY) or at the
+ * partition's last row (PARTITION).  Argument and result types and the treatment of NULL arguments are dfgpu_agg_spec's: NULL
+ * arguments are skipped, a frame without a non-NULL value gives NULL (COUNT: 0), COUNT without an argument counts rows, integer
+ * sums wrap, Decimal128 sums wrap at 128 bits, AVG over Decimal128 truncates and is refused beyond 25 digits, Float64 MIN / MAX
+ * order by IEEE totalOrder.  MIN / MAX over Decimal128 compare signed 128-bit values at any precision.  A Float64 SUM / AVG is a
+ * sum of exactly its frame's values in some order — never a difference of two prefix sums.
+ * DFGPU_WINDOW_TILE = the rows one workgroup takes in the segmented scan behind every function (informative: tests place
+ * partitions around its multiples). */
+#define DFGPU_WINDOW_TILE 2048
+typedef enum dfgpu_window_func {
+  DFGPU_WINDOW_ROW_NUMBER = 0, DFGPU_WINDOW_RANK = 1, DFGPU_WINDOW_DENSE_RANK = 2,
+  DFGPU_WINDOW_SUM = 3, DFGPU_WINDOW_COUNT = 4, DFGPU_WINDOW_MIN = 5, DFGPU_WINDOW_MAX = 6, DFGPU_WINDOW_AVG = 7
+} dfgpu_window_func;
+typedef enum dfgpu_window_frame {
+  DFGPU_WINDOW_RANGE_TO_CURRENT = 0, /* RANGE BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW */
+  DFGPU_WINDOW_ROWS_TO_CURRENT = 1,  /* ROWS BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW */
+  DFGPU_WINDOW_PARTITION = 2         /* ... BETWEEN UNBOUNDED PRECEDING AND UNBOUNDED FOLLOWING */
+} dfgpu_window_frame;
+typedef struct dfgpu_window_spec {
+  int32_t func;          /* dfgpu_window_func */
+  int32_t has_arg;       /* 0 = COUNT(*) and the ranking functions */
+  dfgpu_expr arg;        /* argument expression over the input */
+  int32_t frame;         /* dfgpu_window_frame (aggregate functions) */
+  const char* name;      /* output column name */
+} dfgpu_window_spec;
+/* out = the input's columns (zero-copy: the same buffers, dictionaries handed on), then one column per spec, in the input's row
+ * order.  Zero rows and zero specs are valid inputs. */
+int dfgpu_window(dfgpu_table_t input, const int* partition_cols, int n_partition, const int* order_cols, int n_order,
+                 const dfgpu_window_spec* specs, int n_specs, dfgpu_table_t* out);
 
 /* RepartitionExec, Partitioning::Hash (physical-plan/src/repartition/mod.rs:1097-1150):
  * partition = create_hashes(keys; seed 0) % nparts; row order preserved inside each
