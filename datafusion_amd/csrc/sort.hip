@@ -833,34 +833,60 @@ struct Digit {
 };
 struct SortedKeys {
   BufPtr w[MAX_KEY_WORDS];
-  BufPtr idx;
+  BufPtr idx;   // null: the id of element i is i
   int nwords = 0;
 };
+static SortedKeys one_word_keys(BufPtr key, BufPtr idx = nullptr) {
+  SortedKeys k;
+  k.nwords = 1;
+  k.w[0] = std::move(key);
+  k.idx = std::move(idx);
+  return k;
+}
 
-// digits of a packed key of `total_bits` bits, least significant first; <= 8 bits each, none straddles a word
 // the scatter passes walk their tiles in XCD-contiguous order (device.hpp xcd_tile; measured against tile t on XCD t % 8: - 4 to - 8 %,
 // profiles/r5_sort_phases.md)
-static int sort_xcd_map() { return 1; }
-static int max_digit_bits() { return 8; }   // (digit widths and tile sizes were swept in round 2: profiles/r2_radix_sweep.md)
-static std::vector<Digit> key_digits(int total_bits) {
+constexpr int SORT_XCD_MAP = 1;
+constexpr int MAX_DIGIT_BITS = 8;   // (digit widths and tile sizes were swept in round 2: profiles/r2_radix_sweep.md)
+
+// bits [lo_bit, lo_bit + nbits) of key word `word` as ceil(nbits / max_bits) digits of nearly equal width, least significant first
+// (12 bits = 6 + 6: 8 + 4, 4 + 8, 7 + 5 measured within 5 % of it)
+static std::vector<Digit> equal_digits(int word, int lo_bit, int nbits, int max_bits) {
   std::vector<Digit> ds;
-  const int mb = max_digit_bits();
-  for (int w = 0; w * 64 < total_bits; w++) {
-    const int wbits = std::min(64, total_bits - w * 64);
-    const int nd = (wbits + mb - 1) / mb;
-    int pos = 0;
-    for (int d = 0; d < nd; d++) {
-      const int b = (wbits - pos + (nd - d) - 1) / (nd - d);  // spread the bits evenly over the passes
-      ds.push_back({w, pos, b});
-      pos += b;
-    }
+  const int nd = (nbits + max_bits - 1) / max_bits;
+  for (int d = 0, pos = lo_bit; d < nd; d++) {
+    const int b = (lo_bit + nbits - pos + (nd - d) - 1) / (nd - d);
+    ds.push_back({word, pos, b});
+    pos += b;
   }
   return ds;
 }
+// digits of a packed key of `total_bits` bits, least significant first; <= 8 bits each, none straddles a word
+static std::vector<Digit> key_digits(int total_bits) {
+  std::vector<Digit> ds;
+  for (int w = 0; w * 64 < total_bits; w++)
+    for (const Digit& d : equal_digits(w, 0, std::min(64, total_bits - w * 64), MAX_DIGIT_BITS)) ds.push_back(d);
+  return ds;
+}
+// (at most OS_MAX_PASSES) digits of one key word in the form the onesweep kernels take
+static OsDigits os_digits(const std::vector<Digit>& ds) {
+  OsDigits dg{};
+  for (const Digit& d : ds) {
+    dg.shift[dg.n] = d.shift;
+    dg.bits[dg.n] = d.bits;
+    dg.n++;
+  }
+  return dg;
+}
+// row ids 0 .. n-1
+static BufPtr iota_ids(int64_t n) {
+  BufPtr ids = make_buf((size_t)std::max<int64_t>(n, 1) * 4);
+  if (n) k_iota_u32<<<grid_for(n, BLOCK), BLOCK, 0, rt().stream>>>(n, ids->as<uint32_t>());
+  return ids;
+}
 
 // stable LSD radix sort of n (key, idx) elements over the given digits; returns the buffers holding the result
-static SortedKeys radix_sort(SortedKeys in, int64_t n, const std::vector<Digit>& digits, bool want_ids) {
-  const int xcd_map = sort_xcd_map();   // A/B knob of the XCD-contiguous tile order (device.hpp xcd_tile)
+static SortedKeys radix_sort(SortedKeys in, int64_t n, const std::vector<Digit>& digits, bool want_ids = true) {
   Runtime& r = rt();
   if (n <= 1 || digits.empty()) return in;
   const int nwords = in.nwords;
@@ -890,14 +916,137 @@ static SortedKeys radix_sort(SortedKeys in, int64_t n, const std::vector<Digit>&
     scan_u32(counts->as<uint32_t>(), (int64_t)nb * n_tiles, offsets->as<uint64_t>());
     const uint32_t* idx_in = cur.idx ? cur.idx->as<uint32_t>() : nullptr;
     switch (nwords) {
-      case 1: k_rs_scatter2<1, 16><<<grid, BLOCK, 0, r.stream>>>(ck, idx_in, n, dv, d.word, d.shift, d.bits, n_tiles, offsets->as<uint64_t>(), ob, xcd_map); break;
-      case 2: k_rs_scatter2<2, rs_items(2)><<<grid, BLOCK, 0, r.stream>>>(ck, idx_in, n, dv, d.word, d.shift, d.bits, n_tiles, offsets->as<uint64_t>(), ob, xcd_map); break;
-      default: k_rs_scatter2<3, rs_items(3)><<<grid, BLOCK, 0, r.stream>>>(ck, idx_in, n, dv, d.word, d.shift, d.bits, n_tiles, offsets->as<uint64_t>(), ob, xcd_map); break;
+      case 1: k_rs_scatter2<1, 16><<<grid, BLOCK, 0, r.stream>>>(ck, idx_in, n, dv, d.word, d.shift, d.bits, n_tiles, offsets->as<uint64_t>(), ob, SORT_XCD_MAP); break;
+      case 2: k_rs_scatter2<2, rs_items(2)><<<grid, BLOCK, 0, r.stream>>>(ck, idx_in, n, dv, d.word, d.shift, d.bits, n_tiles, offsets->as<uint64_t>(), ob, SORT_XCD_MAP); break;
+      default: k_rs_scatter2<3, rs_items(3)><<<grid, BLOCK, 0, r.stream>>>(ck, idx_in, n, dv, d.word, d.shift, d.bits, n_tiles, offsets->as<uint64_t>(), ob, SORT_XCD_MAP); break;
     }
     DFGPU_HIP(hipGetLastError());
     std::swap(cur, alt);
   }
   return cur;
+}
+
+// ------------------------------------------------------------------------------ the key plan
+static int bits_for(u128 range) {
+  int b = 0;
+  while (range) {
+    b++;
+    range >>= 1;
+  }
+  return b;
+}
+// What a sort knows about its key before any route runs: the key columns with their value ranges, where each sits in the packed key,
+// and the packed key's size.  Every route reads it; none changes it.
+struct KeyPlan {
+  PackCols pc{};
+  bool narrow = false;         // the key's distinct values fit 63 bits: it is packed as ONE mixed-radix word (k_pack_keys64)
+  uint64_t key_space = 0;      // number of values that word can take (0 when not narrow)
+  int total_bits = 0, nwords = 1;
+  int64_t key_col_bytes = 0;   // bytes of the key columns as they lie in the input
+  std::vector<Digit> digits;   // of the packed key, least significant first
+};
+// the column's values can be read back from the packed key (decoded by sort_emit_row / lsd_emit_keys, compared plainly by
+// k_key_limit_mask_plain); what a route asks of `mult` beyond this is its own business
+static bool key_reads_back(const PackCol& c) { return !c.valid && !c.has_null_bit && is_integer_like(c.type) && c.range != 0; }
+static int64_t key_row_bytes(const PackCols& pc) {
+  int64_t b = 0;
+  for (int k = 0; k < pc.n; k++) b += type_width(pc.c[k].type);
+  return b;
+}
+
+// checks the sort keys and, unless the result is empty anyway, measures them: value ranges -> field widths and positions (last key
+// column = least significant)
+static KeyPlan plan_sort_keys(const Table& in, const std::vector<int>& key_cols, const uint8_t* desc, const uint8_t* nulls_first, bool empty_result) {
+  Runtime& r = rt();
+  const int64_t n = in.nrows;
+  DFGPU_CHECK(!key_cols.empty() && (int)key_cols.size() <= MAX_SORT_KEYS, "bad number of sort keys");
+  KeyPlan kp;
+  PackCols& pc = kp.pc;
+  pc.n = (int)key_cols.size();
+  // signed integer key columns without NULLs take their ranges from the column's cached statistics (column_stats, shared with the
+  // join's map gating and the dynamic filter: computed once per immutable table); anything else is reduced here
+  bool from_stats = true;
+  for (int k = 0; k < pc.n; k++) {
+    DFGPU_CHECK(key_cols[k] >= 0 && key_cols[k] < (int)in.cols.size(), "sort key column out of range");
+    const Column& c = in.cols[key_cols[k]];
+    DFGPU_CHECK(c.field.type != DFGPU_BOOL, "Boolean sort keys are not supported on the GPU path");
+    DFGPU_CHECK(!c.dict || c.dict->sorted, "ORDER BY on a dictionary-encoded string column needs a dictionary in ascending order (index order must be string order)");
+    pc.c[k] = PackCol{c.ptr(), c.valid_words(), c.field.type, desc[k] != 0, nulls_first[k] != 0, c.validity != nullptr, 0, 0, 0, 0};
+    from_stats &= !c.validity && (c.field.type == DFGPU_INT32 || c.field.type == DFGPU_DATE32 || c.field.type == DFGPU_INT64);
+    kp.key_col_bytes += n * type_width(c.field.type);
+  }
+  if (empty_result) return kp;
+  std::vector<u128> h;
+  int grid = 1;
+  if (from_stats) {
+    h.resize((size_t)pc.n * 2);
+    for (int k = 0; k < pc.n; k++) {
+      const Column& c = in.cols[key_cols[k]];
+      const ColStats st = column_stats(const_cast<Column&>(c), n);  // fills the column's shared cache; the rows do not change
+      const bool w32 = c.field.type != DFGPU_INT64;
+      h[(size_t)k * 2] = w32 ? (u128)((uint32_t)(int32_t)st.min ^ 0x80000000u) : (u128)((uint64_t)st.min ^ 0x8000000000000000ull);
+      h[(size_t)k * 2 + 1] = w32 ? (u128)((uint32_t)(int32_t)st.max ^ 0x80000000u) : (u128)((uint64_t)st.max ^ 0x8000000000000000ull);
+    }
+  } else {
+    grid = grid_for(n, BLOCK * 4);
+    BufPtr rb = make_buf((size_t)grid * pc.n * 2 * sizeof(u128));
+    {
+      ProfileScope ps("sort_key_ranges", kp.key_col_bytes);
+      k_key_ranges<<<grid, BLOCK, 0, r.stream>>>(pc, n, rb->as<u128>());
+      DFGPU_HIP(hipGetLastError());
+    }
+    h.resize((size_t)grid * pc.n * 2);
+    d2h(h.data(), rb->ptr, h.size() * sizeof(u128));
+  }
+  int pos = 0;
+  u128 product = 1;
+  for (int k = pc.n - 1; k >= 0; k--) {
+    u128 mn = ~(u128)0, mx = 0;
+    for (int b = 0; b < grid; b++) {
+      mn = std::min(mn, h[((size_t)b * pc.n + k) * 2]);
+      mx = std::max(mx, h[((size_t)b * pc.n + k) * 2 + 1]);
+    }
+    PackCol& c = pc.c[k];
+    if (mn > mx) mn = mx = 0;  // no valid row
+    const u128 base = c.desc ? mx : mn;
+    c.base_lo = (uint64_t)base;
+    c.base_hi = (uint64_t)(base >> 64);
+    c.bits = bits_for(mx - mn);
+    c.shift = pos;
+    pos += c.bits + (c.has_null_bit ? 1 : 0);
+    // mixed radix (one-word keys): this column's digit range and the product of the ranges behind it
+    const u128 span = mx - mn + 1;
+    c.range = span > (u128)0x7FFFFFFFFFFFFFFFull ? 0 : (uint64_t)span;
+    c.mult = product > (u128)0x7FFFFFFFFFFFFFFFull ? 0 : (uint64_t)product;
+    if (c.range == 0 || c.type == DFGPU_DECIMAL128) product = ~(u128)0;
+    else if (product <= ((u128)1 << 63)) product *= (u128)c.range * (c.has_null_bit ? 2 : 1);
+  }
+  DFGPU_CHECK(pos <= 64 * MAX_KEY_WORDS, "packed sort key longer than 192 bits is not supported on the GPU path");
+  // `product` = number of distinct key values the mixed-radix packing can produce; it is used when that fits 63 bits
+  kp.narrow = product <= ((u128)1 << 63);
+  kp.key_space = kp.narrow ? (uint64_t)product : 0;
+  kp.total_bits = kp.narrow ? bits_for(product - 1) : pos;
+  kp.nwords = std::max(1, (kp.total_bits + 63) / 64);
+  kp.digits = key_digits(kp.total_bits);
+  return kp;
+}
+
+// the packed keys of all n rows, written into sk's words (again, where a route has used them as scratch)
+static void pack_sort_keys(const KeyPlan& kp, int64_t n, SortedKeys& sk) {
+  Runtime& r = rt();
+  sk.idx.reset();
+  if (kp.narrow) {
+    // row ids stay implicit until the first radix pass (radix_sort: idx_in == null means id = position); the TopK narrowing
+    // reads the key words only and numbers its survivors afresh
+    ProfileScope ps("sort_pack_keys", kp.key_col_bytes + n * 8);
+    k_pack_keys64<<<grid_for(n, BLOCK * 2), BLOCK, 0, r.stream>>>(kp.pc, n, sk.w[0]->as<uint64_t>());
+  } else {
+    sk.idx = make_buf((size_t)n * 4);
+    ProfileScope ps("sort_pack_keys", kp.key_col_bytes + n * (kp.nwords * 8 + 4));
+    k_pack_keys<<<grid_for(n, BLOCK), BLOCK, 0, r.stream>>>(kp.pc, n, kp.nwords, sk.w[0]->as<uint64_t>(), kp.nwords > 1 ? sk.w[1]->as<uint64_t>() : nullptr,
+                                                           kp.nwords > 2 ? sk.w[2]->as<uint64_t>() : nullptr, sk.idx->as<uint32_t>());
+  }
+  DFGPU_HIP(hipGetLastError());
 }
 
 // ------------------------------------------------------------------------------ top digits in HBM, the rest in LDS
@@ -1332,8 +1481,6 @@ __global__ __launch_bounds__(BLOCK, (sizeof(LK) == 4 ? 4 : 3)) void k_local_sort
   }
 }
 
-static SortedKeys radix_sort(SortedKeys in, int64_t n, const std::vector<Digit>& digits, bool want_ids = true);
-
 // ------------------------------------------------------------------------------ the k-th smallest of m one-word keys, on the device
 // MSD radix select by ONE workgroup: eight 8-bit digits from the top, a 256-bin histogram in LDS per digit over the keys that still
 // share the chosen prefix.  The TopK uses it twice: the c-th smallest of its 16 K samples is the limit of the marking pass (round 5
@@ -1499,72 +1646,84 @@ static BufPtr small_sort_ids(const SortedKeys& sk, int64_t n) {
   return out;
 }
 
-// row ids of a one-word key in sorted order by "top digits in HBM + buckets in LDS"; null when that does not apply (then
-// `clobbered` tells whether the key buffer was used as scratch by the top passes and has to be packed again)
-static BufPtr sorted_ids_local(const SortedKeys& sk, int64_t n, uint64_t key_space, bool& clobbered) {
-  Runtime& r = rt();
-  clobbered = false;
-  // key_space = number of values the mixed-radix key can take (0: the key is not of that kind).  Buckets are key / width with
-  // width = ceil(key_space / 2^top_bits): equal slices of the key space whatever its size, ~2300 rows each when keys spread evenly
-  int top_bits = 0;
-  while (top_bits < 32 && (n >> top_bits) > 2304) top_bits += 8;
-  if (sk.nwords != 1 || n < 2 || n >= 0xFFFFFFFFll || key_space < 2 || (key_space >> top_bits) < 2) return nullptr;
-  const int64_t n_buckets = (int64_t)1 << top_bits;
-  const uint64_t width = (key_space + (uint64_t)n_buckets - 1) / (uint64_t)n_buckets;
-  int low_bits = 0;
-  while (low_bits < 64 && ((width - 1) >> low_bits)) low_bits++;
-  if (low_bits == 0) return nullptr;
-  SortedKeys cur = sk;
-  if (top_bits) {
+// How the two-level sorts cut a one-word key of `key_space` values (0: the key is not of that kind) over n rows into buckets: bucket =
+// key / width with width = ceil(key_space / 2^top_bits) — equal slices of the key space whatever its size, ~2300 rows each when keys
+// spread evenly; the 8-bit top digits are sorted by passes through HBM, the low_bits inside a bucket by one workgroup in LDS
+struct BucketCut {
+  bool applies = false;   // (false: fewer than two key values per bucket)
+  int top_bits = 0, low_bits = 0;
+  int64_t n_buckets = 1;
+  uint64_t width = 0;
+  std::vector<Digit> top_digits() const {   // of key / width, least significant first
     std::vector<Digit> top;
     for (int pos = 0; pos < top_bits; pos += 8) top.push_back({0, pos, std::min(8, top_bits - pos), width});
-    cur = radix_sort(sk, n, top);
-    clobbered = true;
+    return top;
   }
-  BufPtr starts = make_zero_buf((size_t)n_buckets * 4), ends = make_zero_buf((size_t)n_buckets * 4), mx = make_zero_buf(4);
+};
+static BucketCut cut_buckets(int64_t n, uint64_t key_space) {
+  BucketCut c;
+  while (c.top_bits < 32 && (n >> c.top_bits) > 2304) c.top_bits += 8;
+  if ((key_space >> c.top_bits) < 2) return c;
+  c.n_buckets = (int64_t)1 << c.top_bits;
+  c.width = (key_space + (uint64_t)c.n_buckets - 1) / (uint64_t)c.n_buckets;
+  while (c.low_bits < 64 && ((c.width - 1) >> c.low_bits)) c.low_bits++;
+  c.applies = c.low_bits != 0;
+  return c;
+}
+// where every bucket of the top-sorted keys starts and ends, and the size of the largest (read back: beyond LS_CAP the keys are skewed
+// and the bucket sort does not apply)
+struct BucketBounds {
+  BufPtr starts, ends;
+  unsigned largest = 0;
+};
+static BucketBounds bucket_bounds(const BufPtr& key, int64_t n, const BucketCut& cut) {
+  Runtime& r = rt();
+  BucketBounds b;
+  b.starts = make_zero_buf((size_t)cut.n_buckets * 4);
+  b.ends = make_zero_buf((size_t)cut.n_buckets * 4);
+  BufPtr mx = make_zero_buf(4);
   {
     ProfileScope ps("sort_bucket_bounds", n * 8);
-    k_bucket_bounds<<<grid_for(n, BLOCK), BLOCK, 0, r.stream>>>(cur.w[0]->as<uint64_t>(), n, div_by(width), starts->as<uint32_t>(), ends->as<uint32_t>());
-    k_bucket_max<<<grid_for(n_buckets, BLOCK), BLOCK, 0, r.stream>>>(starts->as<uint32_t>(), ends->as<uint32_t>(), n_buckets, mx->as<unsigned>());
+    k_bucket_bounds<<<grid_for(n, BLOCK), BLOCK, 0, r.stream>>>(key->as<uint64_t>(), n, div_by(cut.width), b.starts->as<uint32_t>(), b.ends->as<uint32_t>());
+    k_bucket_max<<<grid_for(cut.n_buckets, BLOCK), BLOCK, 0, r.stream>>>(b.starts->as<uint32_t>(), b.ends->as<uint32_t>(), cut.n_buckets, mx->as<unsigned>());
   }
-  unsigned largest = 0;
-  d2h(&largest, mx->ptr, 4);
-  if (largest > (unsigned)LS_CAP) return nullptr;  // skewed keys: the caller finishes with the all-HBM passes
+  d2h(&b.largest, mx->ptr, 4);
+  return b;
+}
+
+// row ids of a one-word key in sorted order by "top digits in HBM + buckets in LDS"; null when that does not apply (then
+// `clobbered` tells whether the key buffer was used as scratch by the top passes and has to be packed again)
+static BufPtr sorted_ids_local(const SortedKeys& sk, int64_t n, const KeyPlan& kp, bool& clobbered) {
+  Runtime& r = rt();
+  clobbered = false;
+  const BucketCut cut = cut_buckets(n, kp.key_space);
+  if (sk.nwords != 1 || n < 2 || n >= 0xFFFFFFFFll || kp.key_space < 2 || !cut.applies) return nullptr;
+  SortedKeys cur = sk;
+  if (cut.top_bits) {
+    cur = radix_sort(sk, n, cut.top_digits());
+    clobbered = true;
+  }
+  const BucketBounds bb = bucket_bounds(cur.w[0], n, cut);
+  if (bb.largest > (unsigned)LS_CAP) return nullptr;  // skewed keys: the caller finishes with the all-HBM passes
   BufPtr out = make_buf((size_t)n * 4);
   ProfileScope ps("sort_local_buckets", n * 16);
-  const unsigned lg = (unsigned)std::min<int64_t>(n_buckets, (int64_t)r.num_cus * 16);
+  const unsigned lg = (unsigned)std::min<int64_t>(cut.n_buckets, (int64_t)r.num_cus * 16);
   const uint32_t* idp = cur.idx ? cur.idx->as<uint32_t>() : nullptr;
-  if (low_bits <= 32) k_local_sort<uint32_t><<<lg, BLOCK, 0, r.stream>>>(cur.w[0]->as<uint64_t>(), idp, starts->as<uint32_t>(), ends->as<uint32_t>(), n_buckets, width, low_bits, out->as<uint32_t>());
-  else k_local_sort<uint64_t><<<lg, BLOCK, 0, r.stream>>>(cur.w[0]->as<uint64_t>(), idp, starts->as<uint32_t>(), ends->as<uint32_t>(), n_buckets, width, low_bits, out->as<uint32_t>());
+  if (cut.low_bits <= 32) k_local_sort<uint32_t><<<lg, BLOCK, 0, r.stream>>>(cur.w[0]->as<uint64_t>(), idp, bb.starts->as<uint32_t>(), bb.ends->as<uint32_t>(), cut.n_buckets, cut.width, cut.low_bits, out->as<uint32_t>());
+  else k_local_sort<uint64_t><<<lg, BLOCK, 0, r.stream>>>(cur.w[0]->as<uint64_t>(), idp, bb.starts->as<uint32_t>(), bb.ends->as<uint32_t>(), cut.n_buckets, cut.width, cut.low_bits, out->as<uint32_t>());
   DFGPU_HIP(hipGetLastError());
   return out;
 }
 
 // (key, row id) pairs sorted by bits [lo_bit, lo_bit + nbits) of the key — the radix partitioning of the LDS hash join
 // (radix_join.hip): nbits / 8 stable passes.  `idx` may be null on entry: the row id of pair i is then i.
+// 6-bit digits: a 64-way scatter of a 4096-row tile writes 64-row runs; 256-way passes cost 2x per pass (profiles/r2_radix_sweep.md)
 void radix_sort_pairs(BufPtr& key, BufPtr& idx, int64_t n, int lo_bit, int nbits) {
   if (n <= 1 || nbits <= 0) {
-    if (!idx) {
-      idx = make_buf((size_t)std::max<int64_t>(n, 1) * 4);
-      if (n) k_iota_u32<<<grid_for(n, BLOCK), BLOCK, 0, rt().stream>>>(n, idx->as<uint32_t>());
-    }
+    if (!idx) idx = iota_ids(n);
     return;
   }
-  std::vector<Digit> digits;
-  // 6-bit digits: a 64-way scatter of a 4096-row tile writes 64-row runs; 256-way passes cost 2x per pass (profiles/r2_radix_sweep.md)
-  const int mb = 6;
-  const int nd = (nbits + mb - 1) / mb;
-  int pos = lo_bit;
-  for (int d = 0; d < nd; d++) {
-    const int b = (lo_bit + nbits - pos + (nd - d) - 1) / (nd - d);
-    digits.push_back({0, pos, b});
-    pos += b;
-  }
-  SortedKeys in;
-  in.nwords = 1;
-  in.w[0] = key;
-  in.idx = idx;
-  SortedKeys out = radix_sort(in, n, digits);
+  SortedKeys out = radix_sort(one_word_keys(key, idx), n, equal_digits(0, lo_bit, nbits, 6));
   key = out.w[0];
   idx = out.idx;
 }
@@ -1573,36 +1732,9 @@ void radix_sort_pairs(BufPtr& key, BufPtr& idx, int64_t n, int lo_bit, int nbits
 // does to keys that arrive in no order before it looks them up / sets their bits (join.hip)
 void radix_group_keys(BufPtr& key, int64_t n, int lo_bit, int nbits) {
   if (n <= 1 || nbits <= 0) return;
-  std::vector<Digit> digits;
-  const int mb = 6, nd = (nbits + mb - 1) / mb;
-  int pos = lo_bit;
-  for (int d = 0; d < nd; d++) {
-    const int b = (lo_bit + nbits - pos + (nd - d) - 1) / (nd - d);
-    digits.push_back({0, pos, b});
-    pos += b;
-  }
-  SortedKeys in;
-  in.nwords = 1;
-  in.w[0] = key;
-  key = radix_sort(in, n, digits, /*want_ids=*/false).w[0];
+  key = radix_sort(one_word_keys(key), n, equal_digits(0, lo_bit, nbits, 6), /*want_ids=*/false).w[0];
 }
 
-static int bits_for(u128 range) {
-  int b = 0;
-  while (range) {
-    b++;
-    range >>= 1;
-  }
-  return b;
-}
-
-static Table sort_table(const Table& in, const std::vector<int>& key_cols, const uint8_t* desc, const uint8_t* nulls_first, int64_t fetch);
-// the rows of `in` in ascending order of the given key columns (stable); for the library's own use (strings.hip orders the distinct
-// strings of a dictionary by their prefix words)
-Table sort_table_ascending(const Table& in, const std::vector<int>& key_cols) {
-  const std::vector<uint8_t> zeros(key_cols.size(), 0);
-  return sort_table(in, key_cols, zeros.data(), zeros.data(), -1);
-}
 __global__ __launch_bounds__(BLOCK) void k_build_records16(PackLayout L, int64_t n, uint4* __restrict__ rec) {
   for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
     uint64_t sl[2];
@@ -1610,26 +1742,43 @@ __global__ __launch_bounds__(BLOCK) void k_build_records16(PackLayout L, int64_t
     rec[i] = uint4{(unsigned)sl[0], (unsigned)(sl[0] >> 32), (unsigned)sl[1], (unsigned)(sl[1] >> 32)};
   }
 }
-// the carried sort's last step: bucket bounds off the top-sorted keys, then one workgroup per bucket sorts it in LDS and writes the OUTPUT
-// (key columns decoded from the sorted key, the record's fields from the records).  false = a bucket is too large for LDS (skewed keys).
-static bool carried_emit(const Table& in, const std::vector<int>& key_cols, const PackCols& pc, const std::vector<int>& payload, const std::vector<int>& order,
-                         const PackLayout& L, const BufPtr& cur_key, const BufPtr& cur_rec, const BufPtr& cur_idx, int64_t n, int64_t n_buckets, uint64_t width,
-                         int low_bits, Table& out) {
-  Runtime& r = rt();
-  BufPtr starts = make_zero_buf((size_t)n_buckets * 4), ends = make_zero_buf((size_t)n_buckets * 4), mx = make_zero_buf(4);
-  {
-    ProfileScope ps("sort_bucket_bounds", n * 8);
-    k_bucket_bounds<<<grid_for(n, BLOCK), BLOCK, 0, r.stream>>>(cur_key->as<uint64_t>(), n, div_by(width), starts->as<uint32_t>(), ends->as<uint32_t>());
-    k_bucket_max<<<grid_for(n_buckets, BLOCK), BLOCK, 0, r.stream>>>(starts->as<uint32_t>(), ends->as<uint32_t>(), n_buckets, mx->as<unsigned>());
+// ------------------------------------------------------------------------------ what the carried sorts share
+// sort.carried, the form of the carried sort.  Unset / "o…" = onesweep top passes (where it declines, the ids form takes over); "0" = none;
+// "p…" = the records travel through three-kernel top passes (measured: the passes lose more than the take they save, 11.1 ms against
+// 9.9 for 150 M orders); anything else ("i…") = row ids through the passes, records taken by row id INSIDE the bucket sort
+enum class CarriedMode { Onesweep, Ids, Passes, Off };
+static CarriedMode carried_mode() {
+  const std::string s = option_str("sort.carried", "");
+  if (s.empty() || s[0] == 'o') return CarriedMode::Onesweep;
+  return s[0] == '0' ? CarriedMode::Off : s[0] == 'p' ? CarriedMode::Passes : CarriedMode::Ids;
+}
+// the carried sorts are for tables of this many rows (below that the take's lines are cache hits)
+static int64_t carried_min_rows() { return option_int("sort.carried_min_rows", policy().rows_worth_a_pass()); }
+
+// the columns that are not among `key_cols` as ONE record per row (records.hpp)
+struct RecordPlan {
+  std::vector<int> payload, order;   // the columns; field q of the record is column payload[order[q]]
+  PackLayout L{};
+  int R = 0;                         // record bytes
+  bool ok = true;                    // (false: the columns do not fit a record)
+  int payload_bytes() const {
+    int b = 0;
+    for (int q = 0; q < L.n; q++) b += L.width[q];
+    return b;
   }
-  unsigned largest = 0;
-  d2h(&largest, mx->ptr, 4);
-  if (largest > (unsigned)LS_CAP) return false;  // skewed keys: the caller's paths (the packed keys are intact)
-  // the output columns and who writes them
+};
+static RecordPlan plan_payload_record(const Table& in, const std::vector<int>& key_cols) {
+  RecordPlan rp;
+  for (int c = 0; c < (int)in.cols.size(); c++)
+    if (std::find(key_cols.begin(), key_cols.end(), c) == key_cols.end()) rp.payload.push_back(c);
+  if (!rp.payload.empty()) rp.ok = plan_record_layout(in, rp.payload, rp.L, rp.R, rp.order);
+  return rp;
+}
+// the output columns and who writes them: the key columns are decoded from the sorted key, the record's fields split into the others
+static SortEmit plan_emit(const Table& in, const std::vector<int>& key_cols, const PackCols& pc, const RecordPlan& rp, int64_t n, Table& out) {
   out.cols.assign(in.cols.size(), Column{});
   SortEmit e{};
   e.n_keys = pc.n;
-  int out_bytes = 0;
   for (int k = 0; k < pc.n; k++) {
     const int c = key_cols[(size_t)k];
     if (!out.cols[(size_t)c].data) out.cols[(size_t)c] = alloc_like(in.cols[(size_t)c], n);
@@ -1639,109 +1788,100 @@ static bool carried_emit(const Table& in, const std::vector<int>& key_cols, cons
     e.key_base[k] = pc.c[k].base_lo;
     e.key_mult[k] = pc.c[k].mult;
     e.key_div[k] = div_by(pc.c[k].mult);
-    out_bytes += type_width(in.cols[(size_t)c].field.type);
   }
-  e.rec = cur_rec->as<uint4>();
-  e.fields = L;
-  for (int q = 0; q < L.n; q++) {
-    const int c = payload[(size_t)order[(size_t)q]];
+  e.fields = rp.L;
+  for (int q = 0; q < rp.L.n; q++) {
+    const int c = rp.payload[(size_t)rp.order[(size_t)q]];
     out.cols[(size_t)c] = alloc_like(in.cols[(size_t)c], n);
     e.fields.dst[q] = out.cols[(size_t)c].data->ptr;
-    out_bytes += L.width[q];
   }
+  return e;
+}
+
+// the carried sort's last step: bucket bounds off the top-sorted keys, then one workgroup per bucket sorts it in LDS and writes the OUTPUT
+// (key columns decoded from the sorted key, the record's fields from the records).  false = a bucket is too large for LDS (skewed keys).
+// cur_idx null: a row's id is its position — in the top passes' order, or of a one-bucket input
+static bool carried_emit(const Table& in, const std::vector<int>& key_cols, const PackCols& pc, const RecordPlan& rp, const BucketCut& cut, const BufPtr& cur_key,
+                         const BufPtr& cur_rec, const BufPtr& cur_idx, int64_t n, Table& out) {
+  Runtime& r = rt();
+  const BucketBounds bb = bucket_bounds(cur_key, n, cut);
+  if (bb.largest > (unsigned)LS_CAP) return false;  // skewed keys: the caller's paths
+  SortEmit e = plan_emit(in, key_cols, pc, rp, n, out);
+  e.rec = cur_rec->as<uint4>();
   {
-    ProfileScope ps("sort_local_emit", n * (int64_t)(8 + 16 + out_bytes));
-    const unsigned lg = (unsigned)std::min<int64_t>(n_buckets, (int64_t)r.num_cus * 16);
-    const uint32_t* idp = cur_idx ? cur_idx->as<uint32_t>() : nullptr;   // (null: a row's id is its position — in the top passes' order, or of a one-bucket input)
-    if (low_bits <= 32) k_local_sort<uint32_t, true><<<lg, BLOCK, 0, r.stream>>>(cur_key->as<uint64_t>(), idp, starts->as<uint32_t>(), ends->as<uint32_t>(), n_buckets, width, low_bits, nullptr, e);
-    else k_local_sort<uint64_t, true><<<lg, BLOCK, 0, r.stream>>>(cur_key->as<uint64_t>(), idp, starts->as<uint32_t>(), ends->as<uint32_t>(), n_buckets, width, low_bits, nullptr, e);
+    ProfileScope ps("sort_local_emit", n * (int64_t)(8 + 16 + key_row_bytes(pc) + rp.payload_bytes()));
+    const unsigned lg = (unsigned)std::min<int64_t>(cut.n_buckets, (int64_t)r.num_cus * 16);
+    auto launch = [&](auto kern) {
+      kern<<<lg, BLOCK, 0, r.stream>>>(cur_key->as<uint64_t>(), cur_idx ? cur_idx->as<uint32_t>() : nullptr, bb.starts->as<uint32_t>(), bb.ends->as<uint32_t>(), cut.n_buckets,
+                                       cut.width, cut.low_bits, nullptr, e);
+    };
+    if (cut.low_bits <= 32) launch(k_local_sort<uint32_t, true>);
+    else launch(k_local_sort<uint64_t, true>);
     DFGPU_HIP(hipGetLastError());
   }
   DFGPU_HIP(hipStreamSynchronize(r.stream));
   return true;
 }
+// what the two carried sorts ask before they start: enough rows, every key column read back from ONE mixed-radix word, the other columns
+// in one 16-byte record (`rp`), a bucket cut (`cut`)
+static bool carried_applies(const Table& in, const std::vector<int>& key_cols, const KeyPlan& kp, int64_t n, int64_t max_rows, RecordPlan& rp, BucketCut& cut) {
+  if (n < carried_min_rows() || n < 2 || n >= max_rows || kp.key_space < 2) return false;
+  for (int k = 0; k < kp.pc.n; k++)
+    if (!key_reads_back(kp.pc.c[k]) || kp.pc.c[k].mult == 0) return false;
+  rp = plan_payload_record(in, key_cols);
+  if (rp.payload.empty() || !rp.ok || rp.R != 16) return false;
+  cut = cut_buckets(n, kp.key_space);
+  return cut.applies;
+}
 
-// the carried sort (see sort_table); false = does not apply (nothing was touched: `keys` are intact)
-static bool sort_carried(const Table& in, const std::vector<int>& key_cols, const PackCols& pc, const BufPtr& keys, int64_t n, uint64_t key_space, Table& out,
-                         bool& clobbered) {
+// The carried sort in its older forms (round 4): a full sort whose key is one mixed-radix word over integer / date columns without NULLs
+// and whose OTHER columns fit a 16-byte record.  The record travels with the key through the top passes (the first pass reads it from
+// the source columns — "passes") or, the default of the two, row ids travel and the records are fetched by row id ("ids"); the bucket
+// sort in LDS writes the OUTPUT: key columns decoded from the sorted key, the record's fields from the records.  No separate take: orders
+// by (o_orderdate, o_orderkey DESC) 9.9 ms against 11.9 (the take alone was 5.7: a random line per row, profiles/r3_sort_clustered.md).
+// false = does not apply; `clobbered` then tells whether `keys` were scratch of the top passes and have to be packed again
+static bool sort_carried(const Table& in, const std::vector<int>& key_cols, const KeyPlan& kp, const BufPtr& keys, int64_t n, Table& out, bool& clobbered) {
   Runtime& r = rt();
   clobbered = false;
-  // DFGPU_SORT_CARRIED: 0 = off; passes = the records travel through the top passes (measured: the passes lose more than the take
-  // they save, 11.1 ms against 9.9 for 150 M orders); default = row ids through the passes as before, records taken by row id INSIDE the bucket sort
-  const std::string mode_s = option_str("sort.carried", "");
-  const char* mode_env = mode_s.empty() ? nullptr : mode_s.c_str();
-  const bool off = mode_env && mode_env[0] == '0';
-  const bool through_passes = mode_env && mode_env[0] == 'p';
-  const int64_t min_rows = option_int("sort.carried_min_rows", policy().rows_worth_a_pass());   // (below that the take's lines are cache hits)
-  if (off || n < min_rows || n < 2 || n >= 0xFFFFFFFFll || key_space < 2) return false;
-  // every key column can be read back from the packed key
-  for (int k = 0; k < pc.n; k++) {
-    const PackCol& c = pc.c[k];
-    const bool int_like = c.type == DFGPU_INT32 || c.type == DFGPU_DATE32 || c.type == DFGPU_UINT32 || c.type == DFGPU_INT64 || c.type == DFGPU_UINT64 || c.type == DFGPU_UINT8;
-    if (c.valid || c.has_null_bit || !int_like || c.range == 0 || c.mult == 0) return false;
-  }
-  // the other columns: one 16-byte record
-  std::vector<int> payload;
-  for (int c = 0; c < (int)in.cols.size(); c++)
-    if (std::find(key_cols.begin(), key_cols.end(), c) == key_cols.end()) payload.push_back(c);
-  PackLayout L{};
-  int R = 0;
-  std::vector<int> order;
-  if (payload.empty() || !plan_record_layout(in, payload, L, R, order) || R != 16) return false;
-  // buckets as sorted_ids_local cuts them
-  int top_bits = 0;
-  while (top_bits < 32 && (n >> top_bits) > 2304) top_bits += 8;
-  if ((key_space >> top_bits) < 2) return false;
-  const int64_t n_buckets = (int64_t)1 << top_bits;
-  const uint64_t width = (key_space + (uint64_t)n_buckets - 1) / (uint64_t)n_buckets;
-  int low_bits = 0;
-  while (low_bits < 64 && ((width - 1) >> low_bits)) low_bits++;
-  if (low_bits == 0) return false;
+  const CarriedMode mode = carried_mode();
+  RecordPlan rp;
+  BucketCut cut;
+  if (mode == CarriedMode::Off || !carried_applies(in, key_cols, kp, n, 0xFFFFFFFFll, rp, cut)) return false;
   constexpr int ITEMS = 8;   // rows per thread of the record-carrying pass (4: 7.06 ms, 8: 6.75 ms, 16: 9.03 ms for the two passes over 150 M orders)
   const int64_t tile = (int64_t)BLOCK * ITEMS, n_tiles = (n + tile - 1) / tile;
   BufPtr cur_key = keys, cur_rec, cur_idx;
-  if (!through_passes) {
+  if (mode != CarriedMode::Passes) {
     // records in the input's row order (one streaming pass), row ids through the top passes
     cur_rec = make_buf((size_t)n * 16 + 64);
     {
-      int payload_bytes = 0;
-      for (int q = 0; q < L.n; q++) payload_bytes += L.width[q];
-      ProfileScope ps("sort_build_records", n * (int64_t)(payload_bytes + 16));
-      k_build_records16<<<grid_for(n, BLOCK), BLOCK, 0, r.stream>>>(L, n, cur_rec->as<uint4>());
+      ProfileScope ps("sort_build_records", n * (int64_t)(rp.payload_bytes() + 16));
+      k_build_records16<<<grid_for(n, BLOCK), BLOCK, 0, r.stream>>>(rp.L, n, cur_rec->as<uint4>());
       DFGPU_HIP(hipGetLastError());
     }
-    if (top_bits) {
-      SortedKeys sk0;
-      sk0.nwords = 1;
-      sk0.w[0] = keys;
-      std::vector<Digit> top;
-      for (int pos = 0; pos < top_bits; pos += 8) top.push_back({0, pos, std::min(8, top_bits - pos), width});
-      SortedKeys cur = radix_sort(sk0, n, top);
+    if (cut.top_bits) {
+      SortedKeys cur = radix_sort(one_word_keys(keys), n, cut.top_digits());
       clobbered = true;   // (the key buffer was scratch of the passes)
       cur_key = cur.w[0];
       cur_idx = cur.idx;
     }
-  } else if (top_bits) {
+  } else if (cut.top_bits) {
     BufPtr counts = make_buf((size_t)256 * n_tiles * 4), offsets = make_buf((size_t)(256 * n_tiles + 1) * 8);
-    BufPtr key_a = make_buf((size_t)n * 8), key_b = top_bits > 8 ? make_buf((size_t)n * 8) : nullptr;
-    BufPtr rec_a = make_buf((size_t)n * 16), rec_b = top_bits > 8 ? make_buf((size_t)n * 16) : nullptr;
+    BufPtr key_a = make_buf((size_t)n * 8), key_b = cut.top_bits > 8 ? make_buf((size_t)n * 8) : nullptr;
+    BufPtr rec_a = make_buf((size_t)n * 16), rec_b = cut.top_bits > 8 ? make_buf((size_t)n * 16) : nullptr;
     const int grid = (int)std::min<int64_t>(n_tiles, 256 * 8);
-    const DivBy dv = div_by(width);
-    int payload_bytes = 0;
-    for (int q = 0; q < L.n; q++) payload_bytes += L.width[q];
+    const DivBy dv = div_by(cut.width);
     bool first = true;
-    for (int pos = 0; pos < top_bits; pos += 8) {
-      const int bits = std::min(8, top_bits - pos);
+    for (const Digit& d : cut.top_digits()) {
       BufPtr& dst_key = first || cur_key == key_b ? key_a : key_b;
       BufPtr& dst_rec = first || cur_rec == rec_b ? rec_a : rec_b;
-      ProfileScope ps("sort_carried_pass", n * 8 + n * (int64_t)(8 + (first ? payload_bytes : 16) + 8 + 16));
-      k_rs_hist<<<grid, BLOCK, 0, r.stream>>>(cur_key->as<uint64_t>(), n, dv, pos, bits, ITEMS, n_tiles, counts->as<uint32_t>());
-      scan_u32(counts->as<uint32_t>(), (int64_t)(1 << bits) * n_tiles, offsets->as<uint64_t>());
+      ProfileScope ps("sort_carried_pass", n * 8 + n * (int64_t)(8 + (first ? rp.payload_bytes() : 16) + 8 + 16));
+      k_rs_hist<<<grid, BLOCK, 0, r.stream>>>(cur_key->as<uint64_t>(), n, dv, d.shift, d.bits, ITEMS, n_tiles, counts->as<uint32_t>());
+      scan_u32(counts->as<uint32_t>(), (int64_t)(1 << d.bits) * n_tiles, offsets->as<uint64_t>());
       auto launch = [&](auto kern) {
         const size_t lds = (size_t)tile * (8 + 16 + 1);
         DFGPU_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        kern<<<grid, BLOCK, lds, r.stream>>>(cur_key->as<uint64_t>(), first ? nullptr : cur_rec->as<uint4>(), L, n, dv, pos, bits, n_tiles, offsets->as<uint64_t>(),
-                                           dst_key->as<uint64_t>(), dst_rec->as<uint4>(), sort_xcd_map());
+        kern<<<grid, BLOCK, lds, r.stream>>>(cur_key->as<uint64_t>(), first ? nullptr : cur_rec->as<uint4>(), rp.L, n, dv, d.shift, d.bits, n_tiles, offsets->as<uint64_t>(),
+                                           dst_key->as<uint64_t>(), dst_rec->as<uint4>(), SORT_XCD_MAP);
       };
       if (first) launch(k_rs_scatter_kv<ITEMS, true>);
       else launch(k_rs_scatter_kv<ITEMS, false>);
@@ -1752,59 +1892,31 @@ static bool sort_carried(const Table& in, const std::vector<int>& key_cols, cons
     }
   } else {
     cur_rec = make_buf((size_t)n * 16 + 64);   // (a table of one bucket: no top pass to build the records on the way)
-    k_build_records16<<<grid_for(n, BLOCK), BLOCK, 0, r.stream>>>(L, n, cur_rec->as<uint4>());
+    k_build_records16<<<grid_for(n, BLOCK), BLOCK, 0, r.stream>>>(rp.L, n, cur_rec->as<uint4>());
     DFGPU_HIP(hipGetLastError());
   }
-  return carried_emit(in, key_cols, pc, payload, order, L, cur_key, cur_rec, cur_idx, n, n_buckets, width, low_bits, out);
+  return carried_emit(in, key_cols, kp.pc, rp, cut, cur_key, cur_rec, cur_idx, n, out);
 }
 
 // The carried sort with onesweep top passes (round 5; the default form).  The first pass reads the SOURCE columns — the key is packed and
 // the 16-byte record built on the fly — so no packed key array and no record array in input order are ever written: per row the sort
 // moves 12 B (histogram of the key columns) + 24 + 24 B per top pass + 24 + 24 B for the bucket sort that writes the output.
 // false = does not apply, or the keys are skewed beyond what a bucket holds (nothing was touched; the caller's older paths take over).
-static bool sort_carried_onesweep(const Table& in, const std::vector<int>& key_cols, const PackCols& pc, int64_t n, uint64_t key_space, Table& out) {
+static bool sort_carried_onesweep(const Table& in, const std::vector<int>& key_cols, const KeyPlan& kp, int64_t n, Table& out) {
   Runtime& r = rt();
-  const std::string mode_s = option_str("sort.carried", "");   // A/B switch: unset / "o" = this form; "0", "p", "i" = the round-4 forms
-  const char* mode_env = mode_s.empty() ? nullptr : mode_s.c_str();
-  if (mode_env && mode_env[0] != 'o') return false;
-  const int64_t min_rows = option_int("sort.carried_min_rows", policy().rows_worth_a_pass());
-  if (n < min_rows || n < 2 || n >= ((int64_t)1 << 30) || key_space < 2) return false;
-  for (int k = 0; k < pc.n; k++) {   // every key column can be read back from the packed key
-    const PackCol& c = pc.c[k];
-    const bool int_like = c.type == DFGPU_INT32 || c.type == DFGPU_DATE32 || c.type == DFGPU_UINT32 || c.type == DFGPU_INT64 || c.type == DFGPU_UINT64 || c.type == DFGPU_UINT8;
-    if (c.valid || c.has_null_bit || !int_like || c.range == 0 || c.mult == 0) return false;
-  }
-  std::vector<int> payload;
-  for (int c = 0; c < (int)in.cols.size(); c++)
-    if (std::find(key_cols.begin(), key_cols.end(), c) == key_cols.end()) payload.push_back(c);
-  PackLayout L{};
-  int R = 0;
-  std::vector<int> order;
-  if (payload.empty() || !plan_record_layout(in, payload, L, R, order) || R != 16) return false;
-  int top_bits = 0;
-  while (top_bits < 32 && (n >> top_bits) > 2304) top_bits += 8;
-  if (top_bits == 0 || top_bits > 8 * OS_MAX_PASSES || (key_space >> top_bits) < 2) return false;
-  const int64_t n_buckets = (int64_t)1 << top_bits;
-  const uint64_t width = (key_space + (uint64_t)n_buckets - 1) / (uint64_t)n_buckets;
-  int low_bits = 0;
-  while (low_bits < 64 && ((width - 1) >> low_bits)) low_bits++;
-  if (low_bits == 0) return false;
-  const DivBy dv = div_by(width);
-  OsDigits dg{};
-  for (int pos = 0; pos < top_bits; pos += 8) {
-    dg.shift[dg.n] = pos;
-    dg.bits[dg.n] = std::min(8, top_bits - pos);
-    dg.n++;
-  }
+  const PackCols& pc = kp.pc;
+  RecordPlan rp;
+  BucketCut cut;
+  if (carried_mode() != CarriedMode::Onesweep || !carried_applies(in, key_cols, kp, n, (int64_t)1 << 30, rp, cut)) return false;
+  if (cut.top_bits == 0 || cut.top_bits > 8 * OS_MAX_PASSES) return false;
+  const DivBy dv = div_by(cut.width);
+  const OsDigits dg = os_digits(cut.top_digits());
   const int64_t n_tiles = (n + OS_TILE - 1) / OS_TILE;
   BufPtr hist = make_zero_buf((size_t)OS_MAX_PASSES * 256 * 8), bases = make_buf((size_t)OS_MAX_PASSES * 256 * 8);
   BufPtr tickets = make_zero_buf((size_t)OS_MAX_PASSES * 4);
   BufPtr state = make_buf((size_t)n_tiles * 256 * 4);
-  int64_t key_col_bytes = 0, payload_bytes = 0;
-  for (int k = 0; k < pc.n; k++) key_col_bytes += n * (pc.c[k].type == DFGPU_UINT8 ? 1 : type_width(pc.c[k].type));
-  for (int q = 0; q < L.n; q++) payload_bytes += L.width[q];
   {
-    ProfileScope ps("sort_digit_totals", key_col_bytes);
+    ProfileScope ps("sort_digit_totals", kp.key_col_bytes);
     k_os_hist<true><<<r.num_cus * 8, BLOCK, 0, r.stream>>>(nullptr, pc, n, dv, dg, hist->as<unsigned long long>());
     k_os_bases<<<dg.n, BLOCK, 0, r.stream>>>(hist->as<unsigned long long>(), bases->as<unsigned long long>());
     DFGPU_HIP(hipGetLastError());
@@ -1817,20 +1929,20 @@ static bool sort_carried_onesweep(const Table& in, const std::vector<int>& key_c
     const bool first = p == 0;
     BufPtr& dst_key = (first || cur_key == key_b) ? key_a : key_b;
     BufPtr& dst_rec = (first || cur_rec == rec_b) ? rec_a : rec_b;
-    ProfileScope ps("sort_onesweep_pass", first ? key_col_bytes + n * (payload_bytes + 24) : n * 48);
+    ProfileScope ps("sort_onesweep_pass", first ? kp.key_col_bytes + n * (int64_t)(rp.payload_bytes() + 24) : n * 48);
     DFGPU_HIP(hipMemsetAsync(state->ptr, 0, (size_t)n_tiles * 256 * 4, r.stream));
     if (first)
-      k_os_pass<true><<<grid, BLOCK, 0, r.stream>>>(nullptr, nullptr, pc, L, n, dv, dg.shift[p], dg.bits[p], n_tiles, bases->as<unsigned long long>() + p * 256,
+      k_os_pass<true><<<grid, BLOCK, 0, r.stream>>>(nullptr, nullptr, pc, rp.L, n, dv, dg.shift[p], dg.bits[p], n_tiles, bases->as<unsigned long long>() + p * 256,
                                                     state->as<uint32_t>(), tickets->as<unsigned>() + p, dst_key->as<uint64_t>(), dst_rec->as<uint4>());
     else
-      k_os_pass<false><<<grid, BLOCK, 0, r.stream>>>(cur_key->as<uint64_t>(), cur_rec->as<uint4>(), pc, L, n, dv, dg.shift[p], dg.bits[p], n_tiles,
+      k_os_pass<false><<<grid, BLOCK, 0, r.stream>>>(cur_key->as<uint64_t>(), cur_rec->as<uint4>(), pc, rp.L, n, dv, dg.shift[p], dg.bits[p], n_tiles,
                                                      bases->as<unsigned long long>() + p * 256, state->as<uint32_t>(), tickets->as<unsigned>() + p, dst_key->as<uint64_t>(),
                                                      dst_rec->as<uint4>());
     DFGPU_HIP(hipGetLastError());
     cur_key = dst_key;
     cur_rec = dst_rec;
   }
-  return carried_emit(in, key_cols, pc, payload, order, L, cur_key, cur_rec, nullptr, n, n_buckets, width, low_bits, out);
+  return carried_emit(in, key_cols, pc, rp, cut, cur_key, cur_rec, nullptr, n, out);
 }
 
 // The digit-totals pass of the AHEAD form: the input in COARSE segments of `cf` FINE segments of `fine` rows; per fine segment the counts
@@ -1897,11 +2009,11 @@ __global__ void k_lsd_units(const unsigned long long* __restrict__ off1, int64_t
 // number) decides every tie among the columns before it exactly as the input order does (ASC) or as the reversed input order does (DESC),
 // and no column after it matters — so it and everything behind it leave the key, and the first pass reads the rows back to front for DESC.
 // `ORDER BY o_orderdate, o_orderkey DESC` over orders is then a 12-bit sort.  false = does not apply (nothing was touched).
-static bool sort_lsd_carried(const Table& in, const std::vector<int>& key_cols, const PackCols& pc, int64_t n, Table& out) {
+static bool sort_lsd_carried(const Table& in, const std::vector<int>& key_cols, const KeyPlan& kp, int64_t n, Table& out) {
   Runtime& r = rt();
+  const PackCols& pc = kp.pc;
   if (!option_on("sort.lsd", true)) return false;
-  const int64_t min_rows = option_int("sort.carried_min_rows", policy().rows_worth_a_pass());
-  if (n < min_rows || n < 2 || n >= ((int64_t)1 << 30)) return false;
+  if (n < carried_min_rows() || n < 2 || n >= ((int64_t)1 << 30)) return false;
   // the key columns that stay
   int kept = pc.n, reverse = 0;
   for (int k = 0; k < pc.n; k++) {
@@ -1919,68 +2031,30 @@ static bool sort_lsd_carried(const Table& in, const std::vector<int>& key_cols, 
   u128 product = 1;
   for (int k = kept - 1; k >= 0; k--) {
     PackCol& c = kc.c[k];
-    const bool int_like = c.type == DFGPU_INT32 || c.type == DFGPU_DATE32 || c.type == DFGPU_UINT32 || c.type == DFGPU_INT64 || c.type == DFGPU_UINT64 || c.type == DFGPU_UINT8;
-    if (c.valid || c.has_null_bit || !int_like || c.range == 0) return false;   // (the key columns are read back from the key)
+    if (!key_reads_back(c)) return false;
     c.mult = (uint64_t)product;
     product *= (u128)c.range;
     if (product > ((u128)1 << 32)) return false;
   }
   if (product < 2) return false;
   const int total_bits = bits_for(product - 1);
-  const int n_pass = (total_bits + 7) / 8;
-  if (n_pass > OS_MAX_PASSES) return false;
-  OsDigits dg{};
-  for (int p = 0, pos = 0; p < n_pass; p++) {   // digits of (nearly) equal width: 12 bits = 6 + 6 (8 + 4, 4 + 8, 7 + 5 measured within 5 % of it)
-    const int b = (total_bits - pos + (n_pass - p) - 1) / (n_pass - p);
-    dg.shift[p] = pos;
-    dg.bits[p] = b;
-    pos += b;
-    dg.n++;
-  }
+  if ((total_bits + 7) / 8 > OS_MAX_PASSES) return false;
+  const OsDigits dg = os_digits(equal_digits(0, 0, total_bits, 8));
   // the record: every other column (the dropped key columns among them) + the key word
-  std::vector<int> kept_cols(key_cols.begin(), key_cols.begin() + kept), payload;
-  for (int c = 0; c < (int)in.cols.size(); c++)
-    if (std::find(kept_cols.begin(), kept_cols.end(), c) == kept_cols.end()) payload.push_back(c);
-  PackLayout L{};
-  int R = 0, key_off = 0;
-  std::vector<int> order;
-  if (!payload.empty()) {
-    if (!plan_record_layout(in, payload, L, R, order)) return false;
-    int bytes = 0;
-    for (int q = 0; q < L.n; q++) bytes = std::max(bytes, L.offset[q] + L.width[q]);
-    key_off = (bytes + 3) / 4 * 4;
-  }
+  const RecordPlan rp = plan_payload_record(in, std::vector<int>(key_cols.begin(), key_cols.begin() + kept));
+  const PackLayout& L = rp.L;
+  if (!rp.ok) return false;
+  int bytes = 0;
+  for (int q = 0; q < L.n; q++) bytes = std::max(bytes, L.offset[q] + L.width[q]);
+  const int key_off = (bytes + 3) / 4 * 4;
   const int rec_bytes = (key_off + 4 + 7) / 8 * 8;
   if (rec_bytes > 32) return false;
   const int w2 = rec_bytes <= 16 ? 0 : rec_bytes - 16;
   for (int k = 0; k < kept; k++)   // a key column listed twice, or kept and dropped: leave it to the general paths
     for (int j = k + 1; j < pc.n; j++)
       if (key_cols[(size_t)k] == key_cols[(size_t)j]) return false;
-  // output columns and who writes them
-  out.cols.assign(in.cols.size(), Column{});
-  SortEmit e{};
-  e.n_keys = kept;
-  int64_t key_col_bytes = 0, row_bytes = 0;
-  for (int k = 0; k < kept; k++) {
-    const int c = key_cols[(size_t)k];
-    out.cols[(size_t)c] = alloc_like(in.cols[(size_t)c], n);
-    e.key_dst[k] = out.cols[(size_t)c].data->ptr;
-    e.key_type[k] = kc.c[k].type;
-    e.key_desc[k] = kc.c[k].desc;
-    e.key_base[k] = kc.c[k].base_lo;
-    e.key_mult[k] = kc.c[k].mult;
-    e.key_div[k] = div_by(kc.c[k].mult);
-    const int w = kc.c[k].type == DFGPU_UINT8 ? 1 : type_width(kc.c[k].type);
-    key_col_bytes += n * w;
-    row_bytes += w;
-  }
-  e.fields = L;
-  for (int q = 0; q < L.n; q++) {
-    const int c = payload[(size_t)order[(size_t)q]];
-    out.cols[(size_t)c] = alloc_like(in.cols[(size_t)c], n);
-    e.fields.dst[q] = out.cols[(size_t)c].data->ptr;
-    row_bytes += L.width[q];
-  }
+  const SortEmit e = plan_emit(in, key_cols, kc, rp, n, out);
+  const int64_t key_col_bytes = n * key_row_bytes(kc), row_bytes = key_row_bytes(kc) + rp.payload_bytes();
   const int64_t n_tiles = (n + OS_TILE - 1) / OS_TILE;
   BufPtr tickets = make_zero_buf((size_t)OS_MAX_PASSES * 4);
   // two passes over at most 13 bits: every unit's offsets ahead of time (k_lsd_joint), no look-back
@@ -2073,290 +2147,209 @@ static bool sort_lsd_carried(const Table& in, const std::vector<int>& key_cols, 
   return true;
 }
 
+// ------------------------------------------------------------------------------ TopK: the rows that can still be among the first k
+// What a narrowing leaves: the survivors' packed keys with ids 0 .. m-1 of their own, and `remap` from those to the input's row ids
+// (null: the narrowing did not apply).  Survivors keep the input's order, so the sort of their keys stays stable.
+struct Survivors {
+  SortedKeys keys;
+  BufPtr remap;
+  int64_t m = 0;
+};
+// the ids of the rows whose bit is set in `mask`, in input order, and their number `m`; null (m is still set) when fewer than
+// `at_least` or more than `at_most` are set
+static BufPtr compact_mask(const BufPtr& mask, int64_t n, int64_t at_least, int64_t at_most, int64_t& m) {
+  const int64_t n_words = (n + 63) / 64;
+  BufPtr prefix = make_buf((size_t)(n_words + 1) * 8);
+  scan_mask_popcounts(mask->as<uint64_t>(), nullptr, n, prefix->as<uint64_t>());
+  m = (int64_t)read_u64(prefix->as<uint64_t>() + n_words);
+  if (m < at_least || m > at_most) return nullptr;
+  BufPtr ids = make_buf((size_t)(m ? m : 1) * 8);
+  mask_to_ids(mask->as<uint64_t>(), prefix->as<uint64_t>(), n, m, ids->as<int64_t>());
+  return ids;
+}
+
+// TopK by a sampled limit (one-word keys, >= 1 Mi rows): the keys of 16 K evenly spaced rows give a limit that a few thousand rows
+// stay under; ONE pass over the key columns marks them (no packed key array is ever written), and the rest of the sort
+// sees only those.  The k-th smallest key lies under the c-th smallest of S samples unless fewer than k of the n keys do —
+// c is chosen so that ~c n / S >> k rows are expected there; if the marked rows are fewer than k (never seen) or too many
+// (a few distinct keys: ties), it declines and the radix select takes over.
+// (16 K samples: with 64 K, picking the c-th smallest took 0.3 ms of a 1.3 ms TopK; with 16 K the limit lets ~10 K rows per million
+//  through instead of ~2.5 K, which the survivors' sort does not notice: 1.30 -> 0.96 ms; 8 K: 0.94, 4 K: 1.06)
+static Survivors topk_by_sampled_limit(const KeyPlan& kp, int64_t n, int64_t n_out) {
+  Runtime& r = rt();
+  const PackCols& pc = kp.pc;
+  const int64_t S = 1 << 14, every = n / S;
+  const int64_t c = std::min<int64_t>(S, (n_out * S + n - 1) / n * 2 + 16);
+  if (!kp.narrow || n < (1 << 20) || c >= S / 4) return {};
+  BufPtr d_sample = make_buf((size_t)S * 8);
+  const int64_t n_words = (n + 63) / 64;
+  BufPtr mask = make_buf(bitmap_bytes(n));
+  const int top_shift = kp.total_bits > 0 ? ((std::min(kp.total_bits, 64) - 1) / 8) * 8 : 0;
+  BufPtr d_limit = make_buf(16);   // [0] the c-th smallest sample, [1] the second narrowing's limit
+  uint64_t* limit = d_limit->as<uint64_t>();
+  {
+    // the c-th smallest of the samples, selected on the device (k_select_kth): nothing crosses PCIe before the marking pass
+    ProfileScope ps("topk_limit_sample", S * 16);
+    k_pack_keys64_rows<<<grid_for(S, BLOCK), BLOCK, 0, r.stream>>>(pc, nullptr, every, S, d_sample->as<uint64_t>());
+    k_select_kth<<<1, SELECT_THREADS, 0, r.stream>>>(d_sample->as<uint64_t>(), S, c, top_shift, limit);
+    DFGPU_HIP(hipGetLastError());
+  }
+  {
+    ProfileScope ps("topk_limit_pass", kp.key_col_bytes + n / 8);
+    bool plain_keys = n < ((int64_t)1 << 32);
+    for (int k = 0; k < pc.n; k++) plain_keys = plain_keys && key_reads_back(pc.c[k]);
+    if (plain_keys) k_key_limit_mask_plain<<<grid_for(n_words, (BLOCK / WAVE) * 4), BLOCK, 0, r.stream>>>(pc, n, limit, mask->as<uint64_t>());
+    else k_key_limit_mask<<<grid_for(n_words, BLOCK / WAVE), BLOCK, 0, r.stream>>>(pc, n, limit, mask->as<uint64_t>());
+    DFGPU_HIP(hipGetLastError());
+  }
+  Survivors sv;
+  sv.remap = compact_mask(mask, n, n_out, std::max<int64_t>(1 << 22, 64 * n_out), sv.m);
+  if (!sv.remap) return {};
+  sv.keys = one_word_keys(make_buf((size_t)sv.m * 8));
+  k_pack_keys64_rows<<<grid_for(sv.m, BLOCK), BLOCK, 0, r.stream>>>(pc, sv.remap->as<int64_t>(), 0, sv.m, sv.keys.w[0]->as<uint64_t>());
+  sv.keys.idx = iota_ids(sv.m);
+  DFGPU_HIP(hipGetLastError());
+  // ---- second narrowing: the rows that passed are narrowed once more, by a limit sampled among THEM, down to what one workgroup
+  // sorts in LDS (a few hundred rows); too few (never seen) or too many (ties) and the radix passes sort all who passed the first
+  if (sv.m > SMALL_SORT_CAP && sv.m <= ((int64_t)1 << 22) && option_on("sort.topk_second_narrowing", true)) {
+    BufPtr cursor = make_zero_buf(4);
+    const SortedKeys s2 = one_word_keys(make_buf((size_t)SMALL_SORT_CAP * 8), make_buf((size_t)SMALL_SORT_CAP * 4));
+    {
+      // (the limit: the c2-th smallest of up to 16 K evenly spaced survivors, as for the first pass — the exact n_out-th smallest of
+      // all 150 K survivors would be six passes of one workgroup over them, 0.4 ms)
+      ProfileScope ps("topk_second_narrowing", sv.m * 8 * 2);
+      const int64_t S2 = std::min<int64_t>(S, sv.m), every2 = sv.m / S2;
+      const int64_t c2 = std::min<int64_t>(S2, (n_out * S2 + sv.m - 1) / sv.m * 2 + 16);
+      k_strided_u64<<<grid_for(S2, BLOCK), BLOCK, 0, r.stream>>>(sv.keys.w[0]->as<uint64_t>(), every2, S2, d_sample->as<uint64_t>());
+      k_select_kth<<<1, SELECT_THREADS, 0, r.stream>>>(d_sample->as<uint64_t>(), S2, c2, top_shift, limit + 1);
+      k_take_le<<<grid_for(sv.m, BLOCK * 4), BLOCK, 0, r.stream>>>(sv.keys.w[0]->as<uint64_t>(), sv.m, limit + 1, cursor->as<unsigned>(), SMALL_SORT_CAP, s2.w[0]->as<uint64_t>(),
+                                                                    s2.idx->as<uint32_t>());
+      DFGPU_HIP(hipGetLastError());
+    }
+    unsigned taken = 0;
+    d2h(&taken, cursor->ptr, 4);
+    if ((int64_t)taken >= n_out && taken <= (unsigned)SMALL_SORT_CAP) {   // (else: ties beyond the LDS sort's capacity — the radix passes sort all survivors)
+      sv.keys = s2;   // (its ids are positions among the first narrowing's survivors: `remap` stays)
+      sv.m = taken;
+    }
+  }
+  return sv;
+}
+
+// TopK by MSD radix select over the packed keys `sk` of all n rows: digit by digit from the top, the rows that can still be among the
+// first n_out are narrowed to the bucket holding the n_out-th
+static Survivors topk_by_radix_select(const KeyPlan& kp, const SortedKeys& sk, int64_t n, int64_t n_out) {
+  Runtime& r = rt();
+  BufPtr state = make_buf((size_t)n + 64);
+  k_fill_bytes<<<grid_for(n, BLOCK), BLOCK, 0, r.stream>>>(1, n, state->as<uint8_t>());
+  BufPtr hist = make_buf(256 * 8);
+  int64_t selected = 0, candidates = n;
+  for (int di = (int)kp.digits.size() - 1; di >= 0 && selected + candidates > std::max<int64_t>(4096, 2 * n_out); di--) {
+    const Digit& d = kp.digits[(size_t)di];
+    DFGPU_HIP(hipMemsetAsync(hist->ptr, 0, 256 * 8, r.stream));
+    ProfileScope ps("topk_select_pass", n * 9);
+    k_select_hist<<<grid_for(n, BLOCK * 4), BLOCK, 0, r.stream>>>(sk.w[d.word]->as<uint64_t>(), state->as<uint8_t>(), n, d.shift, d.bits, hist->as<unsigned long long>());
+    unsigned long long hh[256];
+    d2h(hh, hist->ptr, sizeof hh);
+    int64_t need = n_out - selected, acc = 0;
+    unsigned pivot = (1u << d.bits) - 1u;
+    for (unsigned v = 0; v < (1u << d.bits); v++) {
+      if (acc + (int64_t)hh[v] >= need) { pivot = v; break; }
+      acc += (int64_t)hh[v];
+    }
+    k_select_apply<<<grid_for(n, BLOCK), BLOCK, 0, r.stream>>>(sk.w[d.word]->as<uint64_t>(), state->as<uint8_t>(), n, d.shift, d.bits, pivot);
+    selected += acc;
+    candidates = (int64_t)hh[pivot];
+  }
+  // survivors (selected + remaining candidates)
+  BufPtr mask = make_buf(bitmap_bytes(n));
+  k_state_mask<<<grid_for((n + 63) / 64, BLOCK / WAVE), BLOCK, 0, r.stream>>>(state->as<uint8_t>(), n, mask->as<uint64_t>());
+  Survivors sv;
+  sv.remap = compact_mask(mask, n, 0, n, sv.m);
+  // their packed keys
+  sv.keys.nwords = sk.nwords;
+  dfgpu_field f64w{};
+  f64w.type = DFGPU_UINT64;
+  for (int wd = 0; wd < sk.nwords; wd++) {
+    Column kc;
+    kc.field = f64w;
+    kc.length = n;
+    kc.data = sk.w[wd];
+    sv.keys.w[wd] = gather_column(kc, sv.remap->as<int64_t>(), sv.m, false).data;
+  }
+  sv.keys.idx = iota_ids(sv.m);
+  return sv;
+}
+
+// ------------------------------------------------------------------------------ SortExec / TopK: the routes
+// positions of the m keys of `sk` in sorted order (stable).  `whole`: sk holds all n rows of the input, which the two-level sort may
+// take (and pack again where it used them as scratch and then declined)
+static BufPtr sorted_ids(const KeyPlan& kp, SortedKeys& sk, int64_t n, int64_t m, bool whole, bool small_input) {
+  bool clobbered = false;
+  BufPtr ids;
+  if (m <= SMALL_SORT_CAP && kp.total_bits > 0 && (small_input || m < n) && option_on("sort.small", true)) ids = small_sort_ids(sk, m);   // the whole input, or a TopK's survivors
+  else if (whole) ids = sorted_ids_local(sk, m, kp, clobbered);
+  if (ids) return ids;
+  if (clobbered) pack_sort_keys(kp, n, sk);
+  const SortedKeys sorted = radix_sort(sk, m, kp.digits);
+  return sorted.idx ? sorted.idx : iota_ids(m);   // (no ids: nothing to sort by — one row, or every key column constant — ids are the positions)
+}
+
 static Table sort_table(const Table& in, const std::vector<int>& key_cols, const uint8_t* desc, const uint8_t* nulls_first, int64_t fetch) {
   Runtime& r = rt();
   const int64_t n = in.nrows;
   DFGPU_CHECK(n < 0xFFFFFFFFll, "sort input exceeds u32 row ids");
-  DFGPU_CHECK(!key_cols.empty() && (int)key_cols.size() <= MAX_SORT_KEYS, "bad number of sort keys");
-  PackCols pc{};
-  pc.n = (int)key_cols.size();
-  int64_t key_col_bytes = 0;
-  for (int k = 0; k < pc.n; k++) {
-    DFGPU_CHECK(key_cols[k] >= 0 && key_cols[k] < (int)in.cols.size(), "sort key column out of range");
-    const Column& c = in.cols[key_cols[k]];
-    DFGPU_CHECK(c.field.type != DFGPU_BOOL, "Boolean sort keys are not supported on the GPU path");
-    DFGPU_CHECK(!c.dict || c.dict->sorted, "ORDER BY on a dictionary-encoded string column needs a dictionary in ascending order (index order must be string order)");
-    pc.c[k] = PackCol{c.ptr(), c.valid_words(), c.field.type, desc[k] != 0, nulls_first[k] != 0, c.validity != nullptr, 0, 0, 0, 0};
-    key_col_bytes += n * (c.field.type == DFGPU_UINT8 ? 1 : type_width(c.field.type));
-  }
-  int64_t n_out = fetch >= 0 ? std::min(fetch, n) : n;
-
+  const int64_t n_out = fetch >= 0 ? std::min(fetch, n) : n;
+  const KeyPlan kp = plan_sort_keys(in, key_cols, desc, nulls_first, /*empty_result=*/n_out == 0);
   Table out;
   out.nrows = n_out;
   if (n_out == 0) {
     for (auto& c : in.cols) out.cols.push_back(alloc_like(c, 0));
     return out;
   }
-  // ---- value ranges -> field widths and positions (last key column = least significant)
-  {
-    // value ranges: signed integer key columns without NULLs take them from the column's cached statistics (column_stats, shared
-    // with the join's map gating and the dynamic filter: computed once per immutable table); anything else is reduced here
-    bool from_stats = true;
-    for (int k = 0; k < pc.n; k++) {
-      const Column& c = in.cols[key_cols[k]];
-      from_stats &= !c.validity && (c.field.type == DFGPU_INT32 || c.field.type == DFGPU_DATE32 || c.field.type == DFGPU_INT64);
-    }
-    std::vector<u128> h;
-    int grid = 1;
-    if (from_stats) {
-      h.resize((size_t)pc.n * 2);
-      for (int k = 0; k < pc.n; k++) {
-        const Column& c = in.cols[key_cols[k]];
-        const ColStats st = column_stats(const_cast<Column&>(c), n);  // fills the column's shared cache; the rows do not change
-        const bool w32 = c.field.type != DFGPU_INT64;
-        h[(size_t)k * 2] = w32 ? (u128)((uint32_t)(int32_t)st.min ^ 0x80000000u) : (u128)((uint64_t)st.min ^ 0x8000000000000000ull);
-        h[(size_t)k * 2 + 1] = w32 ? (u128)((uint32_t)(int32_t)st.max ^ 0x80000000u) : (u128)((uint64_t)st.max ^ 0x8000000000000000ull);
-      }
-    } else {
-      grid = grid_for(n, BLOCK * 4);
-      BufPtr rb = make_buf((size_t)grid * pc.n * 2 * sizeof(u128));
-      {
-        ProfileScope ps("sort_key_ranges", key_col_bytes);
-        k_key_ranges<<<grid, BLOCK, 0, r.stream>>>(pc, n, rb->as<u128>());
-        DFGPU_HIP(hipGetLastError());
-      }
-      h.resize((size_t)grid * pc.n * 2);
-      d2h(h.data(), rb->ptr, h.size() * sizeof(u128));
-    }
-    int pos = 0;
-    u128 product = 1;
-    for (int k = pc.n - 1; k >= 0; k--) {
-      u128 mn = ~(u128)0, mx = 0;
-      for (int b = 0; b < grid; b++) {
-        mn = std::min(mn, h[((size_t)b * pc.n + k) * 2]);
-        mx = std::max(mx, h[((size_t)b * pc.n + k) * 2 + 1]);
-      }
-      PackCol& c = pc.c[k];
-      if (mn > mx) mn = mx = 0;  // no valid row
-      const u128 base = c.desc ? mx : mn;
-      c.base_lo = (uint64_t)base;
-      c.base_hi = (uint64_t)(base >> 64);
-      c.bits = bits_for(mx - mn);
-      c.shift = pos;
-      pos += c.bits + (c.has_null_bit ? 1 : 0);
-      // mixed radix (one-word keys): this column's digit range and the product of the ranges behind it
-      const u128 span = mx - mn + 1;
-      c.range = span > (u128)0x7FFFFFFFFFFFFFFFull ? 0 : (uint64_t)span;
-      c.mult = product > (u128)0x7FFFFFFFFFFFFFFFull ? 0 : (uint64_t)product;
-      if (c.range == 0 || c.type == DFGPU_DECIMAL128) product = ~(u128)0;
-      else if (product <= ((u128)1 << 63)) product *= (u128)c.range * (c.has_null_bit ? 2 : 1);
-    }
-    DFGPU_CHECK(pos <= 64 * MAX_KEY_WORDS, "packed sort key longer than 192 bits is not supported on the GPU path");
-    // `product` = number of distinct key values the mixed-radix packing can produce; it is used when that fits 63 bits
-    const bool narrow = product <= ((u128)1 << 63);
-    const uint64_t key_space = narrow ? (uint64_t)product : 0;
-    const int total_bits = narrow ? bits_for(product - 1) : pos;
-    const int nwords = std::max(1, (total_bits + 63) / 64);
-    SortedKeys sk;
-    sk.nwords = nwords;
-    for (int wd = 0; wd < nwords; wd++) sk.w[wd] = make_buf((size_t)n * 8);
-    const bool topk = fetch >= 0 && n > 4096 && n_out < n / 4 && total_bits > 0;
-    auto pack_keys = [&]() {
-    sk.idx.reset();
-    if (narrow) {
-      // row ids stay implicit until the first radix pass (radix_sort: idx_in == null means id = position); the TopK narrowing
-      // reads the key words only and numbers its survivors afresh
-      ProfileScope ps("sort_pack_keys", key_col_bytes + n * 8);
-      k_pack_keys64<<<grid_for(n, BLOCK * 2), BLOCK, 0, r.stream>>>(pc, n, sk.w[0]->as<uint64_t>());
-      DFGPU_HIP(hipGetLastError());
-    } else {
-      sk.idx = make_buf((size_t)n * 4);
-      ProfileScope ps("sort_pack_keys", key_col_bytes + n * (nwords * 8 + 4));
-      k_pack_keys<<<grid_for(n, BLOCK), BLOCK, 0, r.stream>>>(pc, n, nwords, sk.w[0]->as<uint64_t>(), nwords > 1 ? sk.w[1]->as<uint64_t>() : nullptr,
-                                                             nwords > 2 ? sk.w[2]->as<uint64_t>() : nullptr, sk.idx->as<uint32_t>());
-      DFGPU_HIP(hipGetLastError());
-    }
-    };
-    const std::vector<Digit> digits = key_digits(total_bits);  // least significant first
-    BufPtr remap;                                               // survivor position -> original row id (TopK path)
-    int64_t m = n;
-    // ---- TopK by a sampled limit (one-word keys): the keys of 64 K evenly spaced rows give a limit that a few thousand rows
-    // stay under; ONE pass over the key columns marks them (no packed key array is ever written), and the rest of the sort
-    // sees only those.  The k-th smallest key lies under the c-th smallest of S samples unless fewer than k of the n keys do —
-    // c is chosen so that ~c n / S >> k rows are expected there; if the marked rows are fewer than k (never seen) or too many
-    // (a few distinct keys: ties), the radix select below takes over.
-    bool limited = false;
-    if (topk && narrow && n >= (1 << 20)) {
-      // (16 K samples: the host picks the c-th smallest of them — std::nth_element over 64 K took 0.3 ms of a 1.3 ms TopK; with 16 K the
-      //  limit lets ~10 K rows per million through instead of ~2.5 K, which the survivors' sort does not notice: 1.30 -> 0.96 ms; 8 K: 0.94, 4 K: 1.06)
-      const int64_t S = 1 << 14, every = n / S;
-      const int64_t c = std::min<int64_t>(S, (n_out * S + n - 1) / n * 2 + 16);
-      if (c < S / 4) {
-        BufPtr d_sample = make_buf((size_t)S * 8);
-        const int64_t n_words = (n + 63) / 64;
-        BufPtr mask = make_buf(bitmap_bytes(n));
-        BufPtr prefix = make_buf((size_t)(n_words + 1) * 8);
-        const int top_shift = total_bits > 0 ? ((std::min(total_bits, 64) - 1) / 8) * 8 : 0;
-        BufPtr d_limit = make_buf(16);   // [0] the c-th smallest sample, [1] the n_out-th smallest survivor
-        uint64_t* limit = d_limit->as<uint64_t>();
-        {
-          // the c-th smallest of the samples, selected on the device (k_select_kth): nothing crosses PCIe before the marking pass
-          ProfileScope ps("topk_limit_sample", S * 16);
-          k_pack_keys64_rows<<<grid_for(S, BLOCK), BLOCK, 0, r.stream>>>(pc, nullptr, every, S, d_sample->as<uint64_t>());
-          k_select_kth<<<1, SELECT_THREADS, 0, r.stream>>>(d_sample->as<uint64_t>(), S, c, top_shift, limit);
-          DFGPU_HIP(hipGetLastError());
-        }
-        {
-          ProfileScope ps("topk_limit_pass", key_col_bytes + n / 8);
-          bool plain_keys = n < ((int64_t)1 << 32);
-          for (int k = 0; k < pc.n; k++) {
-            const PackCol& c = pc.c[k];
-            plain_keys = plain_keys && !c.valid && !c.has_null_bit && c.range > 0 &&
-                         (c.type == DFGPU_INT32 || c.type == DFGPU_DATE32 || c.type == DFGPU_UINT32 || c.type == DFGPU_INT64 || c.type == DFGPU_UINT64 || c.type == DFGPU_UINT8);
-          }
-          if (plain_keys) k_key_limit_mask_plain<<<grid_for(n_words, (BLOCK / WAVE) * 4), BLOCK, 0, r.stream>>>(pc, n, limit, mask->as<uint64_t>());
-          else k_key_limit_mask<<<grid_for(n_words, BLOCK / WAVE), BLOCK, 0, r.stream>>>(pc, n, limit, mask->as<uint64_t>());
-          DFGPU_HIP(hipGetLastError());
-        }
-        scan_mask_popcounts(mask->as<uint64_t>(), nullptr, n, prefix->as<uint64_t>());
-        const int64_t under = (int64_t)read_u64(prefix->as<uint64_t>() + n_words);
-        if (under >= n_out && under <= std::max<int64_t>(1 << 22, 64 * n_out)) {
-          m = under;
-          remap = make_buf((size_t)m * 8);
-          mask_to_ids(mask->as<uint64_t>(), prefix->as<uint64_t>(), n, m, remap->as<int64_t>());
-          SortedKeys sv;
-          sv.nwords = 1;
-          sv.w[0] = make_buf((size_t)m * 8);
-          k_pack_keys64_rows<<<grid_for(m, BLOCK), BLOCK, 0, r.stream>>>(pc, remap->as<int64_t>(), 0, m, sv.w[0]->as<uint64_t>());
-          sv.idx = make_buf((size_t)m * 4);
-          k_iota_u32<<<grid_for(m, BLOCK), BLOCK, 0, r.stream>>>(m, sv.idx->as<uint32_t>());
-          DFGPU_HIP(hipGetLastError());
-          sk = sv;
-          limited = true;
-          // ---- second narrowing: the rows that passed are narrowed once more, by a limit sampled among THEM, down to what one workgroup
-          // sorts in LDS (a few hundred rows); too few (never seen) or too many (ties) and the radix passes sort all who passed the first
-          if (m > SMALL_SORT_CAP && m <= ((int64_t)1 << 22) && option_on("sort.topk_second_narrowing", true)) {
-            BufPtr cursor = make_zero_buf(4);
-            SortedKeys s2;
-            s2.nwords = 1;
-            s2.w[0] = make_buf((size_t)SMALL_SORT_CAP * 8);
-            s2.idx = make_buf((size_t)SMALL_SORT_CAP * 4);
-            {
-              // (the limit: the c2-th smallest of up to 16 K evenly spaced survivors, as for the first pass — the exact n_out-th smallest of
-              // all 150 K survivors would be six passes of one workgroup over them, 0.4 ms)
-              ProfileScope ps("topk_second_narrowing", m * 8 * 2);
-              const int64_t S2 = std::min<int64_t>(S, m), every2 = m / S2;
-              const int64_t c2 = std::min<int64_t>(S2, (n_out * S2 + m - 1) / m * 2 + 16);
-              k_strided_u64<<<grid_for(S2, BLOCK), BLOCK, 0, r.stream>>>(sv.w[0]->as<uint64_t>(), every2, S2, d_sample->as<uint64_t>());
-              k_select_kth<<<1, SELECT_THREADS, 0, r.stream>>>(d_sample->as<uint64_t>(), S2, c2, top_shift, limit + 1);
-              k_take_le<<<grid_for(m, BLOCK * 4), BLOCK, 0, r.stream>>>(sv.w[0]->as<uint64_t>(), m, limit + 1, cursor->as<unsigned>(), SMALL_SORT_CAP, s2.w[0]->as<uint64_t>(),
-                                                                         s2.idx->as<uint32_t>());
-              DFGPU_HIP(hipGetLastError());
-            }
-            unsigned taken = 0;
-            d2h(&taken, cursor->ptr, 4);
-            if ((int64_t)taken >= n_out && taken <= (unsigned)SMALL_SORT_CAP) {   // (else: ties beyond the LDS sort's capacity — the radix passes sort all survivors)
-              sk = s2;
-              m = taken;
-            }
-          }
-        }
-      }
-    }
-    // a full sort by one mixed-radix word whose other columns fit a 16-byte record: the onesweep carried sort reads the source columns itself
-    // one workgroup sorts it in LDS (below) — unless the carried sorts are forced onto small tables (sort.carried_min_rows=0: their tests)
-    const bool small_input = n <= SMALL_SORT_CAP && option_on("sort.small", true) && option_int("sort.carried_min_rows", 1) != 0;
-    if (!small_input && !topk && !limited && n_out == n && sort_lsd_carried(in, key_cols, pc, n, out)) return out;
-    if (!small_input && !topk && !limited && narrow && nwords == 1 && n_out == n && sort_carried_onesweep(in, key_cols, pc, n, key_space, out)) return out;
-    if (!limited) pack_keys();
-    if (topk && !limited) {
-      // ---- TopK: MSD radix select narrows to the rows that can still be among the first k
-      BufPtr state = make_buf((size_t)n + 64);
-      k_fill_bytes<<<grid_for(n, BLOCK), BLOCK, 0, r.stream>>>(1, n, state->as<uint8_t>());
-      BufPtr hist = make_buf(256 * 8);
-      int64_t selected = 0, candidates = n;
-      for (int di = (int)digits.size() - 1; di >= 0 && selected + candidates > std::max<int64_t>(4096, 2 * n_out); di--) {
-        const Digit& d = digits[(size_t)di];
-        DFGPU_HIP(hipMemsetAsync(hist->ptr, 0, 256 * 8, r.stream));
-        ProfileScope ps("topk_select_pass", n * 9);
-        k_select_hist<<<grid_for(n, BLOCK * 4), BLOCK, 0, r.stream>>>(sk.w[d.word]->as<uint64_t>(), state->as<uint8_t>(), n, d.shift, d.bits, hist->as<unsigned long long>());
-        unsigned long long hh[256];
-        d2h(hh, hist->ptr, sizeof hh);
-        int64_t need = n_out - selected, acc = 0;
-        unsigned pivot = (1u << d.bits) - 1u;
-        for (unsigned v = 0; v < (1u << d.bits); v++) {
-          if (acc + (int64_t)hh[v] >= need) { pivot = v; break; }
-          acc += (int64_t)hh[v];
-        }
-        k_select_apply<<<grid_for(n, BLOCK), BLOCK, 0, r.stream>>>(sk.w[d.word]->as<uint64_t>(), state->as<uint8_t>(), n, d.shift, d.bits, pivot);
-        selected += acc;
-        candidates = (int64_t)hh[pivot];
-      }
-      // compact survivors (selected + remaining candidates), preserving input order
-      const int64_t n_words = (n + 63) / 64;
-      BufPtr mask = make_buf(bitmap_bytes(n));
-      BufPtr prefix = make_buf((size_t)(n_words + 1) * 8);
-      k_state_mask<<<grid_for(n_words, BLOCK / WAVE), BLOCK, 0, r.stream>>>(state->as<uint8_t>(), n, mask->as<uint64_t>());
-      scan_mask_popcounts(mask->as<uint64_t>(), nullptr, n, prefix->as<uint64_t>());
-      m = (int64_t)read_u64(prefix->as<uint64_t>() + n_words);
-      remap = make_buf((size_t)(m ? m : 1) * 8);
-      mask_to_ids(mask->as<uint64_t>(), prefix->as<uint64_t>(), n, m, remap->as<int64_t>());
-      // survivors' packed keys, re-indexed 0..m-1
-      SortedKeys sv;
-      sv.nwords = nwords;
-      dfgpu_field f64w{};
-      f64w.type = DFGPU_UINT64;
-      for (int wd = 0; wd < nwords; wd++) {
-        Column kc;
-        kc.field = f64w;
-        kc.length = n;
-        kc.data = sk.w[wd];
-        sv.w[wd] = gather_column(kc, remap->as<int64_t>(), m, false).data;
-      }
-      // survivor ids 0..m-1 are positions into `remap`
-      sv.idx = make_buf((size_t)(m ? m : 1) * 4);
-      if (m) k_iota_u32<<<grid_for(m, BLOCK), BLOCK, 0, r.stream>>>(m, sv.idx->as<uint32_t>());
-      sk = sv;
-    }
-    std::vector<int> allc(in.cols.size());
-    for (size_t i = 0; i < allc.size(); i++) allc[i] = (int)i;
-    // ---- carried sort (round 4): a full sort whose key is one mixed-radix word over integer / date columns without NULLs and whose
-    // OTHER columns fit a 16-byte record.  The record travels with the key through the top passes (the first pass reads it from the
-    // source columns — or, the default, row ids travel and the records are fetched by row id), the bucket sort in LDS writes the OUTPUT: key
-    // columns decoded from the sorted key, the record's fields from the records.  No separate take: orders by (o_orderdate, o_orderkey DESC)
-    // 9.9 ms against 11.9 (the take alone was 5.7: a random line per row, profiles/r3_sort_clustered.md).
-    if (!small_input && !remap && narrow && nwords == 1 && !sk.idx && n_out == n && m == n) {
-      bool keys_clobbered = false;
-      if (sort_carried(in, key_cols, pc, sk.w[0], n, key_space, out, keys_clobbered)) return out;
-      if (keys_clobbered) pack_keys();   // (skewed keys: the paths below start from the packed keys again)
-    }
-    // (round 3's 'clustered take' — one more stable pass that moved keys AND a 32-byte record per row into the order of the bucket
-    // number's top digit, so that the final take read records from 18 MB groups — measured 17.9 ms against 12.4-13.2 and stayed
-    // opt-in for a round (profiles/r3_sort_clustered.md); round 4 removed it: the carried sort above is what became of the idea)
-    bool clobbered = false;
-    BufPtr sorted_idx;
-    if (m <= SMALL_SORT_CAP && total_bits > 0 && (small_input || m < n) && option_on("sort.small", true)) sorted_idx = small_sort_ids(sk, m);   // the whole input, or a TopK's survivors
-    else if (!remap) sorted_idx = sorted_ids_local(sk, m, key_space, clobbered);
-    if (!sorted_idx) {
-      if (clobbered) pack_keys();
-      SortedKeys sorted = radix_sort(sk, m, digits);
-      if (!sorted.idx) {  // nothing to sort by (one row, or every key column constant): ids are the positions
-        sorted.idx = make_buf((size_t)std::max<int64_t>(m, 1) * 4);
-        if (m) k_iota_u32<<<grid_for(m, BLOCK), BLOCK, 0, r.stream>>>(m, sorted.idx->as<uint32_t>());
-      }
-      sorted_idx = sorted.idx;
-    }
-    if (remap) {  // TopK survivors: positions among the survivors -> row ids of the input
-      BufPtr take_idx = make_buf((size_t)n_out * 8);
-      k_idx_to_i64<<<grid_for(n_out, BLOCK), BLOCK, 0, r.stream>>>(sorted_idx->as<uint32_t>(), remap->as<int64_t>(), n_out, take_idx->as<int64_t>());
-      DFGPU_HIP(hipGetLastError());
-      out.cols = gather_columns(in, allc, take_idx->as<int64_t>(), n_out, false);
-    } else {
-      out.cols = gather_columns(in, allc, nullptr, n_out, false, sorted_idx->as<uint32_t>());
-    }
+  SortedKeys sk;
+  sk.nwords = kp.nwords;
+  for (int wd = 0; wd < kp.nwords; wd++) sk.w[wd] = make_buf((size_t)n * 8);
+  // ---- TopK: narrow the rows first.  The sampled limit reads the source columns; where it declines the radix select reads the packed keys
+  const bool topk = fetch >= 0 && n > 4096 && n_out < n / 4 && kp.total_bits > 0;
+  Survivors sv;
+  if (topk) sv = topk_by_sampled_limit(kp, n, n_out);
+  const bool limited = sv.remap != nullptr;
+  // ---- a full sort: the sorts that carry the rows with the key and write the output themselves.  Up to SMALL_SORT_CAP rows are left to
+  // one workgroup in LDS — unless the carried sorts are forced onto small tables (sort.carried_min_rows=0: their tests)
+  const bool small_input = n <= SMALL_SORT_CAP && option_on("sort.small", true) && option_int("sort.carried_min_rows", 1) != 0;
+  const bool carried = !small_input && !topk && n_out == n;
+  if (carried && sort_lsd_carried(in, key_cols, kp, n, out)) return out;
+  if (carried && kp.narrow && kp.nwords == 1 && sort_carried_onesweep(in, key_cols, kp, n, out)) return out;
+  // ---- everything else sorts row ids by the packed keys
+  if (!limited) pack_sort_keys(kp, n, sk);
+  if (topk && !limited) sv = topk_by_radix_select(kp, sk, n, n_out);
+  if (topk) sk = sv.keys;
+  if (carried && kp.narrow && kp.nwords == 1) {
+    bool keys_clobbered = false;
+    if (sort_carried(in, key_cols, kp, sk.w[0], n, out, keys_clobbered)) return out;
+    if (keys_clobbered) pack_sort_keys(kp, n, sk);   // (skewed keys: the paths below start from the packed keys again)
+  }
+  const BufPtr sorted_idx = sorted_ids(kp, sk, n, topk ? sv.m : n, /*whole=*/!topk, small_input);
+  // ---- take
+  std::vector<int> allc(in.cols.size());
+  for (size_t i = 0; i < allc.size(); i++) allc[i] = (int)i;
+  if (topk) {  // positions among the survivors -> row ids of the input
+    BufPtr take_idx = make_buf((size_t)n_out * 8);
+    k_idx_to_i64<<<grid_for(n_out, BLOCK), BLOCK, 0, r.stream>>>(sorted_idx->as<uint32_t>(), sv.remap->as<int64_t>(), n_out, take_idx->as<int64_t>());
+    DFGPU_HIP(hipGetLastError());
+    out.cols = gather_columns(in, allc, take_idx->as<int64_t>(), n_out, false);
+  } else {
+    out.cols = gather_columns(in, allc, nullptr, n_out, false, sorted_idx->as<uint32_t>());
   }
   DFGPU_HIP(hipStreamSynchronize(r.stream));
   return out;
+}
+// the rows of `in` in ascending order of the given key columns (stable); for the library's own use (strings.hip orders the distinct
+// strings of a dictionary by their prefix words)
+Table sort_table_ascending(const Table& in, const std::vector<int>& key_cols) {
+  const std::vector<uint8_t> zeros(key_cols.size(), 0);
+  return sort_table(in, key_cols, zeros.data(), zeros.data(), -1);
 }
 
 }  // namespace dfgpu

@@ -190,8 +190,8 @@ def test_topk_by_sampled_limit(shape, k):
 def test_sort_carried_records_and_keys_decoded_from_the_packed_key(monkeypatch, shape, mode):
     """the carried sort (sort.hip sort_carried_onesweep / sort_carried; forced here for tables of a few MB): the columns the packed key does
     not hold become ONE 16-byte record per row — travelling with the key through onesweep top passes whose first pass reads the source
-    columns (round 5, the default), fetched by row id inside the LDS bucket sort (DFGPU_SORT_CARRIED=ids, round 4's default) or travelling
-    through the three-kernel passes (DFGPU_SORT_CARRIED=passes) — and the bucket sort writes the output: key columns DECODED from the sorted mixed-radix
+    columns (round 5, the default), fetched by row id inside the LDS bucket sort (sort.carried=ids, round 4's default) or travelling
+    through the three-kernel passes (sort.carried=passes) — and the bucket sort writes the output: key columns DECODED from the sorted mixed-radix
     key (ASC and DESC, dates, negative and unsigned values, UInt8), payload fields from the records.  No separate take runs.  Same stable order as the oracle position by position (ties keep their input order: the payload tells).  Shapes
     it must decline and leave to the other paths: a payload beyond 16 bytes, a nullable key column, buckets beyond the LDS capacity"""
     from datafusion_amd import ops
