@@ -183,9 +183,9 @@ def words_of(col):
     elif pa.types.is_decimal128(t):
         w = np.frombuffer(col.buffers()[1], np.uint64, 2 * (n + col.offset))[2 * col.offset:].reshape(n, 2).copy() if n else np.zeros((0, 2), np.uint64)
     else:
-        width = {4: (np.int32, np.uint32), 8: (np.int64, np.uint64)}[t.bit_width // 8]
+        width = {1: (np.int8, np.uint8), 4: (np.int32, np.uint32), 8: (np.int64, np.uint64)}[t.bit_width // 8]
         raw = np.frombuffer(col.buffers()[1], width[1] if pa.types.is_unsigned_integer(t) else width[0], n + col.offset)[col.offset:] if n else np.zeros(0, width[0])
-        w = raw.astype(np.int64).view(np.uint64).reshape(n, 1) if raw.dtype.itemsize == 4 else raw.view(np.uint64).reshape(n, 1)
+        w = raw.astype(np.int64).view(np.uint64).reshape(n, 1) if raw.dtype.itemsize < 8 else raw.view(np.uint64).reshape(n, 1)
     w = np.where(valid[:, None], w, np.uint64(0))
     return w, valid
 

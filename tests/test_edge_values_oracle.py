@@ -9,6 +9,7 @@ import pytest
 
 from oracle import oracle
 from tests import edge_values as E
+from tests import partition_cases as PC
 
 def total_key(bits: int) -> int:
     """f64::total_cmp as an integer key: positive floats by their bits, negative ones reversed below them (-0.0 just below +0.0)"""
@@ -206,6 +207,98 @@ def test_hash_routing_follows_the_float_bits():
         raw = raw_of(t.column("k"))
         for i in range(t.num_rows):
             assert part[i] == (0 if raw[i] is None else int(hashes[i]) % nparts)
+
+
+_ROUTING = {}
+
+
+def _routing_reference():
+    """the edge-value table of the check above with a second, Int64 key (NULLs in both), and the hashes of its rows over one key and
+    over both in Python integers (tests/partition_cases.py row_hashes), made once"""
+    if not _ROUTING:
+        rng = np.random.default_rng(9)
+        t = pa.table({"k": E.edge_array(rng, 3000, pa.float64(), 0.5, 0.05), "k2": E.edge_array(rng, 3000, pa.int64(), 0.5, 0.05)})
+        raws, types = [raw_of(t.column("k")), raw_of(t.column("k2"))], [pa.float64(), pa.int64()]
+        assert None in raws[0] and None in raws[1] and any(a is None and b is None for a, b in zip(*raws))
+        _ROUTING.update(table=t, one=PC.row_hashes(raws[:1], types[:1]), two=PC.row_hashes(raws, types))
+    return _ROUTING
+
+
+@pytest.mark.parametrize("nparts", PC.ALL_COUNTS)
+def test_hash_routing_is_the_hash_modulo_every_partition_count(nparts):
+    """every count the device partitions into (1..64; tests/test_gpu_partition.py compares with the oracle at each of them): a row goes
+    to hash % nparts as Python integers compute it, over one key and over two, a NULL key leaving the hash as it was (0 for a row of NULLs
+    only); the partitions hold their rows in input order"""
+    ref = _routing_reference()
+    t = ref["table"]
+    for keys, hashes in ((["k"], ref["one"]), (["k", "k2"], ref["two"])):
+        parts, part = oracle.hash_partition(t, keys, nparts)
+        assert [int(h) for h in oracle.create_hashes([t.column(k) for k in keys], 0)] == hashes
+        assert part.tolist() == [h % nparts for h in hashes]
+        assert len(parts) == nparts and sum(p.num_rows for p in parts) == t.num_rows
+        for p, tab in enumerate(parts):
+            E.assert_exact(tab, t.take(pa.array([i for i, h in enumerate(hashes) if h % nparts == p], pa.int64())), ordered=True)
+
+
+@pytest.mark.parametrize("kind", list(PC.KEY_KINDS))
+def test_hashes_of_every_partition_key_kind_in_python_integers(kind):
+    """the key kinds of the partition tests: signed 32-bit values hash as their sign-extended 64-bit word, unsigned ones zero-extended,
+    floats by their bits, a Decimal128 by both words, a second key re-seeds with the first one's hash.  The columns carry the values
+    the tests name: UInt64 at and above 2^63, both zeros and both NaN signs"""
+    t, keys = PC.key_table(kind, PC.N)
+    types = [typ for _, typ, _ in PC.KEY_KINDS[kind]]
+    raws = [raw_of(t.column(k)) for k in keys]
+    assert [int(h) for h in oracle.create_hashes([t.column(k) for k in keys], 0)] == PC.row_hashes(raws, types)
+    assert (None in raws[0]) == (kind == "int64_nullable")
+    if kind == "uint64":
+        assert {2**63, 2**64 - 1} <= set(raws[0])
+    if kind == "float64":
+        assert {E.f64_bits(0.0), E.f64_bits(-0.0), E.QNAN_BITS, E.NEG_QNAN_BITS} <= set(raws[0])
+    for nparts in (3, 17, 64):
+        assert PC.reference(t, keys, nparts)[1].tolist() == [h % nparts for h in PC.row_hashes(raws, types)]
+
+
+def test_partition_cases_are_the_shapes_they_claim():
+    """the case lists of tests/partition_cases.py: the sizes around one tile, the table that needs a second trip through the tile loop,
+    the column counts on both sides of a scatter launch, and view tables whose partitions start off every 16-byte boundary"""
+    assert PC.N == 4099 and PC.N % 4 == 3 and PC.TWO_TRIPS == 2048 * 1024 + 1025
+    assert PC.ceil_div(PC.TWO_TRIPS, PC.TILE) == PC.TILE_GRID + 2 and PC.ceil_div(PC.TWO_TRIPS - PC.TILE - 1, PC.TILE) == PC.TILE_GRID
+    cases = PC.kind_cases()
+    assert len(cases) == len(set(cases)) == 5 * 56 + 5 * 21
+    for kind in PC.KEY_KINDS:
+        assert {(p, n) for k, p, n in cases if k == kind} >= {(p, PC.N) for p in PC.KERNEL_COUNTS} | {(p, n) for p in (3, 17) for n in PC.SIZES}
+    for ncols, key_last in PC.WIDE_CASES:
+        t = PC.wide_table(ncols, key_last)
+        assert t.num_columns == ncols and t.column_names.index("k") == (ncols - 1 if key_last else 0)
+        assert {f.type.bit_width // 8 for f in t.schema} == {1, 4, 8, 16}
+    for name, sizes in PC.VIEW_SIZES.items():
+        t = PC.view_source(name)
+        exp, part = PC.reference(t, [PC.VIEW_KEY], 3)
+        assert [e.num_rows for e in exp] == list(sizes)
+        for e in exp[1:]:      # (the views used) input order is kept, so the ascending columns still ascend, densely enough for the one-pass rank map
+            for c in ("a64", "a32"):
+                a = np.asarray(e.column(c)).astype(np.int64)
+                assert (np.diff(a) > 0).all() and len(a) >= 0.15 * (a[-1] - a[0] + 1)
+    s = PC.VIEW_SIZES
+    assert s["odd"][0] % 2 == 1 and (s["odd"][0] + s["odd"][1]) % 2 == 1
+    assert s["mod4"][0] % 4 == 1 and (s["mod4"][0] + s["mod4"][1]) % 4 == 2
+    assert s["blocks"][1] == s["blocks"][2] == 2 * 4096 + 3 and s["blocks"][0] % 2 == 1
+
+
+def test_byte_hash_of_string_keys_known_answers():
+    """strings.hip hash_bytes as tests/partition_cases.py restates it: the length seeds it, whole little-endian words first, a partial
+    last word zero-padded and marked, so "12345678" and "123456789" and a prefix with a trailing NUL differ"""
+    h = PC.hash_bytes
+    assert h(b"") == PC.fmix64(PC.SEED_BYTES)
+    assert h(b"a") == PC.fmix64(PC.fmix64(1 ^ PC.SEED_BYTES) ^ 0x61 ^ PC.GOLDEN)
+    assert h(b"12345678") == PC.fmix64(PC.fmix64(8 ^ PC.SEED_BYTES) ^ int.from_bytes(b"12345678", "little"))
+    assert len({h(b"12345678"), h(b"123456789"), h(b"a"), h(b"a\0"), h(b"")}) == 5
+    t = PC.odd_key_table("utf8")
+    exp, part = PC.reference(t, ["k"], 17)
+    home = {}
+    for s, p in zip(t.column("k").to_pylist(), part.tolist()):
+        assert home.setdefault(s, p) == p
+    assert home[None] == 0 and len(set(home.values())) > 3
 
 
 def test_span_columns_have_the_exact_span():
