@@ -445,7 +445,7 @@ std::vector<Column> gather_columns(const Table& in, const std::vector<int>& cols
       in_bytes += in.nrows * type_width(c.field.type);
     }
   }
-  const bool pack = packable.size() >= 2 && in_bytes > ((int64_t)256 << 20) && n * 4 >= in.nrows;
+  const bool pack = packable.size() >= 2 && in_bytes > option_int("take.pack_min_bytes", (int64_t)256 << 20) && n * 4 >= in.nrows;
   std::vector<bool> done(cols.size(), false);
   if (pack && n > 0) {
     // widest columns first keeps every field naturally aligned inside the record

@@ -643,6 +643,8 @@ int dfgpu_agg_fused_updates(dfgpu_agg_t h, int64_t* out);
  *   join.radix_partition_rows (2400: build rows per LDS partition on average; test hook: small values give several passes on small inputs)
  *   sort.carried = o|i|p|0 (o), sort.carried_min_rows (rows worth a pass), sort.lsd = 0|1 (1: narrow keys sorted by record passes alone),
  *   sort.lsd_ahead = 0|1 (1: two-pass narrow-key sorts take their offsets from the digit-totals pass instead of a look-back)
+ *   take.pack_min_bytes (256 MiB: a take of several plain columns packs them into row-major records first when the columns taken from
+ *   hold more bytes than this; test hook: 0 packs on small inputs)
  *   parquet.device_decode = 0|1 (1: page headers on the host, levels / runs / values decoded by kernels), parquet.snappy = host|device (host),
  *   parquet.in_flight (4: chunks a scan worker keeps in flight)
  * The same table is read from the environment variable DFGPU_OPTIONS="name=value,name=value" (lower priority than this call).
