@@ -63,8 +63,8 @@ class AggSpec(C.Structure):
 
 
 class WindowSpec(C.Structure):
-    """dfgpu_window_spec (ABI 17)"""
-    _fields_ = [("func", C.c_int32), ("has_arg", C.c_int32), ("arg", Expr), ("frame", C.c_int32), ("name", C.c_char_p)]
+    """dfgpu_window_spec (ABI 18: n = NTILE's buckets / NTH_VALUE's index)"""
+    _fields_ = [("func", C.c_int32), ("has_arg", C.c_int32), ("arg", Expr), ("frame", C.c_int32), ("name", C.c_char_p), ("n", C.c_int64)]
 
 
 class KernelStat(C.Structure):

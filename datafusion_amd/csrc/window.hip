@@ -13,6 +13,27 @@
 //              partition's last row, and turns it into the result type and a validity bit.  When every peer-head bit is set (a
 //              popcount tells) RANGE is ROWS and the pick is skipped.
 // A Float64 sum is a tree of additions over exactly its frame's values (identity 0.0 joins exactly): never a difference of prefixes.
+//
+// PERCENT_RANK / CUME_DIST / NTILE and FIRST_VALUE / LAST_VALUE / NTH_VALUE (ABI 18) take a row's positions from the bitmaps themselves:
+//   words    : per head bitmap two arrays of one int64 per 64-row WORD — last_upto[w] = the row of the last head in words 0..w (the max
+//              scan above over n_words elements), first_from[w] = the row of the first head in words w.., or n (the min scan in reverse)
+//   start(i) : w = i >> 6, b = i & 63;  m = heads[w] & (~0ull >> (63 - b));
+//              m ? (w << 6) + 63 - clz(m) : last_upto[w - 1]          // row 0 is always a head: w == 0 never falls through
+//   end(i)   : m = b == 63 ? 0 : heads[w] & (~0ull << (b + 1));        // never shift by 64
+//              next = m ? (w << 6) + ctz(m) : (w + 1 < n_words ? first_from[w + 1] : n);   return next - 1
+//   dist     : one wave per word; the bitmap word and the two summary entries are one address per wave, 8 bytes are written per row
+//   value    : the same loop; the row picks one row of its frame, gathers the argument there and ballots the validity word
+// No n * 8 position array is built for them.  With s / e the first / last row of the row's partition, rows = e - s + 1, ps / pe the
+// first / last row of its peer group and i the row itself (DataFusion 55 functions-window: rank.rs, cume_dist.rs, ntile.rs, nth_value.rs):
+//   percent_rank  (double)(ps - s) / (double)max(rows - 1, 1)                                     Float64, never NULL
+//   cume_dist     (double)(pe - s + 1) / (double)rows                                             Float64, never NULL
+//   ntile(n)      n >= 1; k = min(n, rows); (i - s) * k / rows + 1 (unsigned 64-bit, truncating)  UInt64, never NULL
+// The value functions are RESPECT NULLS over the frame [s, f]: f = i (rows_to_current), f = pe (range_to_current), f = e (partition):
+//   first_value          the argument at s
+//   last_value           the argument at f
+//   nth_value(n), n > 0  the argument at s + n - 1 if that is <= f, otherwise NULL
+//   nth_value(n), n < 0  the argument at f + n + 1 if that is >= s, otherwise NULL
+// A NULL argument at the picked row gives NULL; the value slot under a NULL result is 0.
 #include <climits>
 
 #include "device.hpp"
@@ -152,7 +173,11 @@ enum WinSrc : int {
   WS_NONE = 9,       // no value: COUNT (the validity alone) and ROW_NUMBER-like counts
   WS_BIT = 10,       // `bits`[row] as 0 / 1 (DENSE_RANK: the peer heads)
   WS_START_POS = 11, // `bits`[row] ? row : -inf         (max scan: the last head at or before the row)
-  WS_END_POS = 12    // row is the last or `bits`[row + 1] ? row : +inf   (min scan in reverse: the last row before the next head)
+  WS_END_POS = 12,   // row is the last or `bits`[row + 1] ? row : +inf   (min scan in reverse: the last row before the next head)
+  // over the WORDS of `bits` (n = the number of words):
+  WS_WORD_START = 13, // `bits`[w] ? the row of its highest set bit : -inf   (max scan: the last head in words 0..w)
+  WS_WORD_END = 14    // `bits`[w] ? the row of its lowest set bit : +inf, the last word's no more than `limit`   (min scan in reverse: the
+                      // first head in words w.., or `limit` = the number of rows)
 };
 struct WinIn {
   const void* data;
@@ -162,6 +187,7 @@ struct WinIn {
   int64_t n;
   int src;
   int reverse;             // scan position i is row n - 1 - i (heads must be null)
+  int64_t limit;           // WS_WORD_END
 };
 __device__ __forceinline__ int64_t win_row(const WinIn& in, int64_t i) { return in.reverse ? in.n - 1 - i : i; }
 __device__ __forceinline__ bool win_head(const WinIn& in, int64_t i) { return in.heads && bit_at(in.heads, i); }
@@ -187,6 +213,18 @@ __device__ __forceinline__ WVal<typename Op::V> win_load(const WinIn& in, int64_
     case WS_BIT: lo = bit_at(in.bits, e) ? 1 : 0; break;
     case WS_START_POS: lo = (uint64_t)(bit_at(in.bits, e) ? e : INT64_MIN); break;
     case WS_END_POS: lo = (uint64_t)((e == in.n - 1 || bit_at(in.bits, e + 1)) ? e : INT64_MAX); break;
+    case WS_WORD_START: {
+      const uint64_t b = in.bits[e];
+      lo = (uint64_t)(b ? (e << 6) + 63 - __clzll((long long)b) : INT64_MIN);
+      break;
+    }
+    case WS_WORD_END: {
+      const uint64_t b = in.bits[e];
+      int64_t x = b ? (e << 6) + __ffsll((unsigned long long)b) - 1 : INT64_MAX;
+      if (e == in.n - 1 && x > in.limit) x = in.limit;
+      lo = (uint64_t)x;
+      break;
+    }
   }
   r.v = Op::make(lo, hi);
   return r;
@@ -386,6 +424,115 @@ __global__ __launch_bounds__(BLOCK) void k_window_rank(int mode, const int64_t* 
     out[i] = (uint64_t)((mode == 0 ? i : peer_start[i]) - part_start[i] + 1);
 }
 
+// ------------------------------------------------------------------------------------------------ positions from bitmap words
+// one head bitmap and its per-word summaries (null where the caller's mode does not read them)
+struct WinWords {
+  const uint64_t* heads;
+  const int64_t* last_upto;    // [w] = the row of the last head in words 0..w
+  const int64_t* first_from;   // [w] = the row of the first head in words w.., or n
+};
+// what one wave reads of a WinWords for its word w: one address per wave each
+struct WinWordCtx {
+  uint64_t bits;    // heads[w]
+  int64_t before;   // last_upto[w - 1] (word 0: 0 — row 0 is always a head, it is never taken)
+  int64_t after;    // first_from[w + 1], or n behind the last word
+};
+__device__ __forceinline__ WinWordCtx win_word_ctx(const WinWords& x, int64_t w, int64_t n_words, int64_t n, bool starts, bool ends) {
+  WinWordCtx c;
+  c.bits = x.heads[w];
+  c.before = starts && w > 0 ? x.last_upto[w - 1] : 0;
+  c.after = ends && w + 1 < n_words ? x.first_from[w + 1] : n;
+  return c;
+}
+// the last head at or before row (w << 6) + b
+__device__ __forceinline__ int64_t win_start(const WinWordCtx& c, int64_t w, int b) {
+  const uint64_t m = c.bits & (~0ull >> (63 - b));
+  return m ? (w << 6) + 63 - __clzll((long long)m) : c.before;
+}
+// the last row before the next head behind row (w << 6) + b
+__device__ __forceinline__ int64_t win_end(const WinWordCtx& c, int64_t w, int b) {
+  const uint64_t m = b == 63 ? 0 : c.bits & (~0ull << (b + 1));   // never shift by 64
+  const int64_t next = m ? (w << 6) + __ffsll((unsigned long long)m) - 1 : c.after;
+  return next - 1;
+}
+
+enum WinDist : int { WD_PERCENT_RANK = 0, WD_CUME_DIST = 1, WD_NTILE = 2 };
+// one wave per 64 rows.  NTILE never touches the peer bitmap; PERCENT_RANK reads the peer starts, CUME_DIST the peer ends.
+__global__ __launch_bounds__(BLOCK) void k_window_dist(int mode, WinWords part, WinWords peer, uint64_t buckets, int64_t n, void* __restrict__ out) {
+  const int64_t n_words = (n + 63) >> 6;
+  const int64_t wave = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 6;
+  const int64_t n_waves = ((int64_t)gridDim.x * BLOCK) >> 6;
+  for (int64_t w = wave; w < n_words; w += n_waves) {
+    const int b = (int)lane_id();
+    const int64_t i = (w << 6) + b;
+    const WinWordCtx pc = win_word_ctx(part, w, n_words, n, true, true);
+    WinWordCtx oc{};
+    if (mode != WD_NTILE) oc = win_word_ctx(peer, w, n_words, n, mode == WD_PERCENT_RANK, mode == WD_CUME_DIST);
+    if (i < n) {
+      const int64_t s = win_start(pc, w, b), e = win_end(pc, w, b);
+      const uint64_t rows = (uint64_t)(e - s + 1);
+      if (mode == WD_NTILE) {
+        const uint64_t k = buckets < rows ? buckets : rows;
+        stream_store((uint64_t*)out + i, (uint64_t)(i - s) * k / rows + 1);
+      } else if (mode == WD_PERCENT_RANK) {
+        const int64_t ps = win_start(oc, w, b);
+        stream_store((double*)out + i, (double)(ps - s) / (double)(rows > 1 ? rows - 1 : 1));
+      } else {
+        const int64_t pe = win_end(oc, w, b);
+        stream_store((double*)out + i, (double)(pe - s + 1) / (double)rows);
+      }
+    }
+  }
+}
+
+enum WinPick : int { WP_FIRST = 0, WP_LAST = 1, WP_NTH = 2 };
+template <typename T>
+__device__ __forceinline__ void win_store(T* p, T v) { stream_store(p, v); }
+template <>
+__device__ __forceinline__ void win_store<u128>(u128* p, u128 v) {
+  stream_store((uint4*)p, make_uint4((unsigned)v, (unsigned)(v >> 32), (unsigned)(v >> 64), (unsigned)(v >> 96)));
+}
+template <int WIDTH> struct WinBytes;
+template <> struct WinBytes<1> { typedef uint8_t T; };
+template <> struct WinBytes<4> { typedef uint32_t T; };
+template <> struct WinBytes<8> { typedef uint64_t T; };
+template <> struct WinBytes<16> { typedef u128 T; };
+// one wave per 64 rows: the row picks row p of its frame [s, f] (or none), the result is the argument's bytes there — unchanged,
+// whatever they mean — or NULL (a zeroed value slot and a clear validity bit) where there is no p or the argument at p is NULL.
+// `frame_ends` = the bitmap whose run ends are f (the peer heads: RANGE, the partition heads: PARTITION), null for ROWS (f = the row).
+template <int WIDTH>
+__global__ __launch_bounds__(BLOCK) void k_window_value(int pick, int64_t nth, WinWords part, WinWords frame_ends, const void* __restrict__ arg,
+                                                        const uint64_t* __restrict__ valid, int64_t n, void* __restrict__ out, uint64_t* __restrict__ out_valid) {
+  typedef typename WinBytes<WIDTH>::T T;
+  const int64_t n_words = (n + 63) >> 6;
+  const int64_t wave = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 6;
+  const int64_t n_waves = ((int64_t)gridDim.x * BLOCK) >> 6;
+  const bool need_s = pick != WP_LAST, need_f = pick != WP_FIRST;
+  for (int64_t w = wave; w < n_words; w += n_waves) {
+    const int b = (int)lane_id();
+    const int64_t i = (w << 6) + b;
+    WinWordCtx pc{}, fc{};
+    if (need_s) pc = win_word_ctx(part, w, n_words, n, true, false);
+    if (need_f && frame_ends.heads) fc = win_word_ctx(frame_ends, w, n_words, n, false, true);
+    bool ok = false;
+    if (i < n) {
+      const int64_t s = need_s ? win_start(pc, w, b) : 0;
+      const int64_t f = !need_f ? 0 : frame_ends.heads ? win_end(fc, w, b) : i;
+      int64_t p = -1;
+      if (pick == WP_FIRST) p = s;
+      else if (pick == WP_LAST) p = f;
+      else if (nth > 0) p = nth - 1 <= f - s ? s + (nth - 1) : -1;   // (compared as distances: s + nth cannot overflow)
+      else p = -(nth + 1) <= f - s ? f + (nth + 1) : -1;
+      ok = p >= 0 && (!valid || bit_at(valid, p));
+      T v = 0;
+      if (ok) v = ((const T*)arg)[p];
+      win_store((T*)out + i, v);
+    }
+    const uint64_t bal = ballot64(ok);
+    if (lane_id() == 0) out_valid[w] = bal;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ host
 template <class Op>
 static void run_window_scan(const WinIn& in, void* out_v, uint64_t* out_c, const char* name, int64_t bytes) {
@@ -438,6 +585,12 @@ static const char* win_func_name(int func) {
     case DFGPU_WINDOW_MIN: return "MIN";
     case DFGPU_WINDOW_MAX: return "MAX";
     case DFGPU_WINDOW_AVG: return "AVG";
+    case DFGPU_WINDOW_PERCENT_RANK: return "PERCENT_RANK";
+    case DFGPU_WINDOW_CUME_DIST: return "CUME_DIST";
+    case DFGPU_WINDOW_NTILE: return "NTILE";
+    case DFGPU_WINDOW_FIRST_VALUE: return "FIRST_VALUE";
+    case DFGPU_WINDOW_LAST_VALUE: return "LAST_VALUE";
+    case DFGPU_WINDOW_NTH_VALUE: return "NTH_VALUE";
   }
   throw Error("unknown dfgpu_window_func " + std::to_string(func));
 }
@@ -524,6 +677,17 @@ static Table window_table(const Table& in, const int* partition_cols, int n_part
   const int64_t n_words = (n + 63) / 64;
   DFGPU_CHECK(n_specs >= 0 && (n_specs == 0 || specs != nullptr), "window expressions missing");
   const KeySet part = window_keys(in, partition_cols, n_partition), order = window_keys(in, order_cols, n_order);
+  for (int s = 0; s < n_specs; s++) {   // an unknown function or a bad parameter is an error before anything runs
+    const dfgpu_window_spec& spec = specs[s];
+    const char* fn = win_func_name(spec.func);
+    DFGPU_CHECK(spec.func != DFGPU_WINDOW_NTILE || spec.n >= 1, "NTILE needs a positive number of buckets");
+    if (spec.func == DFGPU_WINDOW_FIRST_VALUE || spec.func == DFGPU_WINDOW_LAST_VALUE || spec.func == DFGPU_WINDOW_NTH_VALUE) {
+      DFGPU_CHECK(spec.has_arg != 0, std::string(fn) + " needs an argument");
+      DFGPU_CHECK(spec.func != DFGPU_WINDOW_NTH_VALUE || spec.n != 0, "NTH_VALUE needs a non-zero n");
+      DFGPU_CHECK(spec.frame == DFGPU_WINDOW_RANGE_TO_CURRENT || spec.frame == DFGPU_WINDOW_ROWS_TO_CURRENT || spec.frame == DFGPU_WINDOW_PARTITION,
+                  "unknown dfgpu_window_frame " + std::to_string(spec.frame));
+    }
+  }
   Table out;
   out.device = in.device;
   out.nrows = n;
@@ -552,6 +716,25 @@ static Table window_table(const Table& in, const int* partition_cols, int n_part
     }
     return slot->as<int64_t>();
   };
+  // the same per 64-row word (PERCENT_RANK .. NTH_VALUE): made when the first function asks, once per bitmap and direction
+  BufPtr part_word_start, peer_word_start, part_word_end, peer_word_end;
+  const auto word_positions = [&](BufPtr& slot, const BufPtr& heads, bool end) -> const int64_t* {
+    if (!slot) {
+      slot = make_buf((size_t)n_words * 8);
+      WinIn pin{nullptr, nullptr, nullptr, heads->as<uint64_t>(), n_words, end ? WS_WORD_END : WS_WORD_START, end ? 1 : 0, n};
+      if (end) run_window_scan<OpMinI64>(pin, slot->ptr, nullptr, "window_word_ends", n_words * 16);
+      else run_window_scan<OpMaxI64>(pin, slot->ptr, nullptr, "window_word_starts", n_words * 16);
+    }
+    return slot->as<int64_t>();
+  };
+  const auto part_words = [&](bool starts, bool ends) {
+    return WinWords{part_heads->as<uint64_t>(), starts ? word_positions(part_word_start, part_heads, false) : nullptr,
+                    ends ? word_positions(part_word_end, part_heads, true) : nullptr};
+  };
+  const auto peer_words = [&](bool starts, bool ends) {
+    return WinWords{peer_heads->as<uint64_t>(), starts ? word_positions(peer_word_start, peer_heads, false) : nullptr,
+                    ends ? word_positions(peer_word_end, peer_heads, true) : nullptr};
+  };
   int peers_unique = -1;   // every peer group is one row: RANGE frames are ROWS frames (asked once, by the first RANGE frame)
   const auto all_peers_unique = [&]() {
     if (peers_unique < 0) {
@@ -570,7 +753,65 @@ static Table window_table(const Table& in, const int* partition_cols, int n_part
     const dfgpu_window_spec& spec = specs[s];
     const std::string name = spec.name ? spec.name : "";
     const int func = spec.func;
-    win_func_name(func);   // (an unknown function is an error before anything runs for it)
+    if (func == DFGPU_WINDOW_PERCENT_RANK || func == DFGPU_WINDOW_CUME_DIST || func == DFGPU_WINDOW_NTILE) {
+      const bool ntile = func == DFGPU_WINDOW_NTILE;
+      Column c = alloc_column(wfld(ntile ? DFGPU_UINT64 : DFGPU_FLOAT64, 0, 0, 0), name, n);
+      c.null_count = 0;
+      if (n > 0) {
+        const WinWords pw = part_words(true, true);
+        const WinWords ow = ntile ? WinWords{nullptr, nullptr, nullptr} : peer_words(func == DFGPU_WINDOW_PERCENT_RANK, func == DFGPU_WINDOW_CUME_DIST);
+        ProfileScope ps("window_dist", n * 8 + n_words * (ntile ? 24 : 40));   // the result; per word a bitmap and two summaries, and the peers' two
+        k_window_dist<<<grid_for(n_words, BLOCK / WAVE), BLOCK, 0, r.stream>>>(ntile ? WD_NTILE : func == DFGPU_WINDOW_PERCENT_RANK ? WD_PERCENT_RANK : WD_CUME_DIST, pw, ow,
+                                                                            (uint64_t)spec.n, n, c.data->ptr);
+        DFGPU_HIP(hipGetLastError());
+      }
+      out.cols.push_back(std::move(c));
+      continue;
+    }
+    if (func == DFGPU_WINDOW_FIRST_VALUE || func == DFGPU_WINDOW_LAST_VALUE || func == DFGPU_WINDOW_NTH_VALUE) {
+      Column arg = datum_to_column(evaluate(spec.arg, in), n, name);
+      DFGPU_CHECK(arg.dict || (arg.field.type != DFGPU_BOOL && arg.field.type != DFGPU_UTF8),
+                  std::string(win_func_name(func)) + "(" + name + ") over " + win_type_name(arg) + " is not supported on the GPU path");
+      const int width = type_width(arg.field.type);
+      dfgpu_field of = arg.field;
+      of.nullable = 1;
+      if (func == DFGPU_WINDOW_LAST_VALUE && spec.frame == DFGPU_WINDOW_ROWS_TO_CURRENT) {   // the argument itself: no launch
+        arg.field = of;
+        arg.name = name;
+        if (arg.null_count < 0) count_nulls(arg);
+        out.cols.push_back(std::move(arg));
+        continue;
+      }
+      Column c = alloc_column(of, name, n, n > 0);
+      c.dict = arg.dict;
+      if (n == 0) {
+        c.null_count = 0;
+        out.cols.push_back(std::move(c));
+        continue;
+      }
+      const int pick = func == DFGPU_WINDOW_FIRST_VALUE ? WP_FIRST : func == DFGPU_WINDOW_LAST_VALUE ? WP_LAST : WP_NTH;
+      const WinWords pw = pick != WP_LAST ? part_words(true, false) : WinWords{nullptr, nullptr, nullptr};
+      WinWords fw{nullptr, nullptr, nullptr};
+      if (pick != WP_FIRST && spec.frame == DFGPU_WINDOW_PARTITION) fw = part_words(false, true);
+      else if (pick != WP_FIRST && spec.frame == DFGPU_WINDOW_RANGE_TO_CURRENT) fw = peer_words(false, true);
+      {
+        // the argument and its validity once, the result and its validity once, per word a bitmap and a summary for each end that is read
+        ProfileScope ps("window_value", n * 2 * width + (arg.validity ? n / 8 : 0) + n / 8 + n_words * 16 * ((pw.heads ? 1 : 0) + (fw.heads ? 1 : 0)));
+        const int g = grid_for(n_words, BLOCK / WAVE);
+        uint64_t* ov = c.validity->as<uint64_t>();
+        switch (width) {
+          case 1: k_window_value<1><<<g, BLOCK, 0, r.stream>>>(pick, spec.n, pw, fw, arg.ptr(), arg.valid_words(), n, c.data->ptr, ov); break;
+          case 4: k_window_value<4><<<g, BLOCK, 0, r.stream>>>(pick, spec.n, pw, fw, arg.ptr(), arg.valid_words(), n, c.data->ptr, ov); break;
+          case 8: k_window_value<8><<<g, BLOCK, 0, r.stream>>>(pick, spec.n, pw, fw, arg.ptr(), arg.valid_words(), n, c.data->ptr, ov); break;
+          case 16: k_window_value<16><<<g, BLOCK, 0, r.stream>>>(pick, spec.n, pw, fw, arg.ptr(), arg.valid_words(), n, c.data->ptr, ov); break;
+          default: throw Error("window value function over a column of " + std::to_string(width) + " bytes per value");
+        }
+        DFGPU_HIP(hipGetLastError());
+      }
+      count_nulls(c);
+      out.cols.push_back(std::move(c));
+      continue;
+    }
     if (func == DFGPU_WINDOW_ROW_NUMBER || func == DFGPU_WINDOW_RANK || func == DFGPU_WINDOW_DENSE_RANK) {
       Column c = alloc_column(wfld(DFGPU_UINT64, 0, 0, 0), name, n);
       c.null_count = 0;

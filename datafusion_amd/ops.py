@@ -32,6 +32,11 @@ WINDOW_FUNCS = {"row_number": 0, "rank": 1, "dense_rank": 2, "sum": 3, "count": 
 WINDOW_RANKING = frozenset(("row_number", "rank", "dense_rank"))
 WINDOW_FRAMES = {"range_to_current": 0, "rows_to_current": 1, "partition": 2}
 WINDOW_TILE = 2048
+# ABI 18: functions of a row's partition and peer-group bounds (no argument, no frame), and picks of the argument at one row of the
+# frame.  ntile and nth_value carry an integer: the function is written ("ntile", 4) / ("nth_value", -2) in a window expression.
+WINDOW_DIST_FUNCS = {"percent_rank": 8, "cume_dist": 9, "ntile": 10}
+WINDOW_VALUE_FUNCS = {"first_value": 11, "last_value": 12, "nth_value": 13}
+WINDOW_PARAM_FUNCS = frozenset(("ntile", "nth_value"))
 PROBE_MODES = {"auto": 0, "two_pass": 1, "single_pass_ordered": 2, "single_pass_unordered": 3, "order_not_needed": 4}
 
 
@@ -245,8 +250,18 @@ def sort(table: DeviceTable, keys, fetch=None) -> DeviceTable:
     return DeviceTable(out)
 
 
+def window_func_code(func) -> int:
+    """dfgpu_window_func of a normalised window function (a name, or (name, n) for ntile / nth_value)"""
+    name = func[0] if isinstance(func, tuple) else func
+    for table in (WINDOW_FUNCS, WINDOW_DIST_FUNCS, WINDOW_VALUE_FUNCS):
+        if name in table:
+            return table[name]
+    raise KeyError(name)
+
+
 def normalize_window_exprs(exprs):
-    """a window expression is (func, arg | None, name, frame); frame None (or left out) = range_to_current, the default under an ORDER BY"""
+    """a window expression is (func, arg | None, name, frame); frame None (or left out) = range_to_current, the default under an ORDER BY.
+    func is a name, or (name, n) for ntile (n buckets) and nth_value (the n-th row of the frame, from its end when negative)."""
     out = []
     for w in exprs or []:
         if len(w) == 3:
@@ -255,18 +270,38 @@ def normalize_window_exprs(exprs):
             raise ValueError(f"a window expression is (func, arg | None, name, frame), not {w!r}")
         func, arg, name, frame = w
         frame = "range_to_current" if frame is None else frame
-        if func not in WINDOW_FUNCS:
-            raise ValueError(f"window function {func!r} is not supported on the GPU path")
+        fname, param = func, None
+        if isinstance(func, (tuple, list)):
+            if len(func) != 2:
+                raise ValueError(f"a window function with a parameter is (name, n), not {func!r}")
+            fname, param = func
+        if not isinstance(fname, str) or not (fname in WINDOW_FUNCS or fname in WINDOW_DIST_FUNCS or fname in WINDOW_VALUE_FUNCS):
+            raise ValueError(f"window function {fname!r} is not supported on the GPU path")
         if frame not in WINDOW_FRAMES:
             raise ValueError(f"window frame {frame!r} is not supported on the GPU path")
-        out.append((func, None if func in WINDOW_RANKING else arg, name, frame))
+        if fname in WINDOW_PARAM_FUNCS:
+            if isinstance(param, bool) or not isinstance(param, int):
+                raise ValueError(f"{fname.upper()} takes an integer: ({fname!r}, n), not {func!r}")
+            if fname == "ntile" and param < 1:
+                raise ValueError("NTILE needs a positive number of buckets")
+            if fname == "nth_value" and param == 0:
+                raise ValueError("NTH_VALUE needs a non-zero n")
+            if not -2**63 <= param < 2**63:
+                raise ValueError(f"{fname.upper()}: {param} does not fit 64 bits")
+            func = (fname, param)
+        elif param is not None or func is not fname:
+            raise ValueError(f"window function {fname!r} takes no parameter: {func!r}")
+        if fname in WINDOW_VALUE_FUNCS and arg is None:
+            raise ValueError(f"{fname.upper()} needs an argument")
+        out.append((func, None if fname in WINDOW_RANKING or fname in WINDOW_DIST_FUNCS else arg, name, frame))
     return out
 
 
 def window(table: DeviceTable, partition_by, order_by, exprs) -> DeviceTable:
     """WindowAggExec / BoundedWindowAggExec over a table already ordered by (partition_by, order_by) — column names or indices; exprs =
-    [(func, arg | None, name, frame)], func in WINDOW_FUNCS, frame in WINDOW_FRAMES.  The result is the input's columns (the same
-    buffers) followed by one column per expression."""
+    [(func, arg | None, name, frame)], func in WINDOW_FUNCS, WINDOW_DIST_FUNCS or WINDOW_VALUE_FUNCS (("ntile", n) / ("nth_value", n)
+    carry their integer), frame in WINDOW_FRAMES.  The result is the input's columns (the same buffers) followed by one column per
+    expression."""
     lib = _lib.init()
     names = table.column_names
     pidx = [table.index_of(c) for c in partition_by or []]
@@ -274,7 +309,7 @@ def window(table: DeviceTable, partition_by, order_by, exprs) -> DeviceTable:
     keep, specs = [], []
     for func, arg, name, frame in normalize_window_exprs(exprs):
         s = WindowSpec()
-        s.func = WINDOW_FUNCS[func]
+        s.func = window_func_code(func)
         s.has_arg = 0 if arg is None else 1
         if arg is not None:
             l = lower(arg, names, table)
@@ -282,6 +317,7 @@ def window(table: DeviceTable, partition_by, order_by, exprs) -> DeviceTable:
             s.arg = l.c
         s.frame = WINDOW_FRAMES[frame]
         s.name = name.encode()
+        s.n = func[1] if isinstance(func, tuple) else 0
         specs.append(s)
     sarr = (WindowSpec * max(1, len(specs)))(*specs)
     out = C.c_void_p()

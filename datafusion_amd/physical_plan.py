@@ -524,7 +524,8 @@ class SortExec(_Unary):
 
 class WindowAggExec(_Unary):
     """WindowAggExec / BoundedWindowAggExec (physical-plan/src/windows/): window_expr = [(func, arg | None, name, frame)] — func one of
-    ops.WINDOW_FUNCS, frame one of ops.WINDOW_FRAMES (None = range_to_current, the default under an ORDER BY) — over
+    ops.WINDOW_FUNCS, ops.WINDOW_DIST_FUNCS or ops.WINDOW_VALUE_FUNCS (("ntile", n) and ("nth_value", n) carry their integer), frame
+    one of ops.WINDOW_FRAMES (None = range_to_current, the default under an ORDER BY) — over
     PARTITION BY partition_by ORDER BY order_by.  partition_by = columns; order_by = columns or (column, descending, nulls_first) as
     SortExec takes them: direction and NULL placement are kept for display only, the operator looks at equality of neighbouring rows.
     The input must arrive ordered by (partition_by, order_by) — the SortExec the planner puts below; the two reference nodes differ
@@ -546,8 +547,10 @@ class WindowAggExec(_Unary):
 
     def detail(self):
         def one(func, arg, name, frame):
-            over = "" if func in ops.WINDOW_RANKING else f" {frame}"
-            return f"{func}({'' if arg is None else repr(arg)}){over} AS {name}"
+            func, param = func if isinstance(func, tuple) else (func, None)
+            over = "" if func in ops.WINDOW_RANKING or func in ops.WINDOW_DIST_FUNCS else f" {frame}"
+            inside = ", ".join(([] if arg is None else [repr(arg)]) + ([] if param is None else [str(param)]))
+            return f"{func}({inside}){over} AS {name}"
         order = ", ".join(f"{c} {'DESC' if d else 'ASC'} NULLS {'FIRST' if nf else 'LAST'}" for c, d, nf in self.order_by)
         return (f"wdw=[{', '.join(one(*w) for w in ops.normalize_window_exprs(self.window_expr))}], "
                 f"partition_by=[{', '.join(str(c) for c in self.partition_by)}], order_by=[{order}]")
@@ -802,8 +805,17 @@ def plan_schema(node):
         if isinstance(node, WindowAggExec):
             fields = list(inp)
             for func, e, n, _ in ops.normalize_window_exprs(node.window_expr):
-                if func in ops.WINDOW_RANKING:
+                func = func[0] if isinstance(func, tuple) else func
+                if func in ops.WINDOW_RANKING or func == "ntile":
                     fields.append(pa.field(n, pa.uint64(), nullable=False))
+                elif func in ops.WINDOW_DIST_FUNCS:
+                    fields.append(pa.field(n, pa.float64(), nullable=False))
+                elif func in ops.WINDOW_VALUE_FUNCS:
+                    t = ops.expr_type(empty, e)
+                    if isinstance(e, Column):      # a dictionary-encoded column keeps its dictionary (the device types its codes)
+                        src = inp.field(inp.get_field_index(e.name) if e.index is None else e.index).type
+                        t = src if pa.types.is_dictionary(src) else t
+                    fields.append(pa.field(n, t, nullable=True))
                 else:
                     fields.append(pa.field(n, _agg_type(func, None if e is None else ops.expr_type(empty, e)), nullable=func != "count"))
             return pa.schema(fields)
@@ -951,6 +963,7 @@ def unsupported_reason(node):
             return None
         try:
             for func, e, n, _ in ops.normalize_window_exprs(node.window_expr):
+                func = func[0] if isinstance(func, tuple) else func
                 if e is None or func == "count":
                     continue
                 try:
@@ -958,6 +971,14 @@ def unsupported_reason(node):
                 except _lib.DfgpuError as err:
                     return f"{func}({e!r}): {err}"
                 except (KeyError, TypeError, ValueError):
+                    continue
+                if func in ops.WINDOW_VALUE_FUNCS:
+                    # window.hip window_table: the argument's bytes are picked whatever they mean (dictionary codes too); Boolean columns
+                    # are bit-packed and Utf8 columns have no fixed width
+                    if pa.types.is_boolean(t):
+                        return f"{func.upper()}({n}) over Boolean is not supported on the GPU path"
+                    if pa.types.is_string(t) or pa.types.is_large_string(t):
+                        return f"{func.upper()}({n}) over Utf8 is not supported on the GPU path"
                     continue
                 if func == "avg" and pa.types.is_decimal128(t) and t.precision + 13 > 38:
                     # window.hip plan_window: the aggregate's refusal (avg_sum_data_type widens to Decimal256 beyond 38 digits)

@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define DFGPU_ABI_VERSION 17
+#define DFGPU_ABI_VERSION 18
 
 /* Arrow C Data Interface (https://arrow.apache.org/docs/format/CDataInterface.html) */
 #ifndef ARROW_C_DATA_INTERFACE
@@ -692,12 +692,32 @@ int dfgpu_sort(dfgpu_table_t input, const int* key_cols, const uint8_t* descendi
  * sums wrap, Decimal128 sums wrap at 128 bits, AVG over Decimal128 truncates and is refused beyond 25 digits, Float64 MIN / MAX
  * order by IEEE totalOrder.  MIN / MAX over Decimal128 compare signed 128-bit values at any precision.  A Float64 SUM / AVG is a
  * sum of exactly its frame's values in some order — never a difference of two prefix sums.
+ * ABI 18 — with s / e the first / last row of the row's partition, rows = e - s + 1, ps / pe the first / last row of its peer group
+ * and i the row itself (functions-window/src/rank.rs, cume_dist.rs, ntile.rs, nth_value.rs):
+ *   PERCENT_RANK  (double)(ps - s) / (double)max(rows - 1, 1)                                          Float64
+ *   CUME_DIST     (double)(pe - s + 1) / (double)rows                                                  Float64
+ *   NTILE         n >= 1; k = min(n, rows); (i - s) * k / rows + 1 (unsigned 64-bit, truncating)       UInt64
+ * never NULL, `arg` and `frame` ignored; each Float64 is ONE IEEE division of two integers below 2^53.  NTILE is not "larger buckets
+ * first": 6 rows and n = 4 give 1,1,2,3,3,4.  n < 1: "NTILE needs a positive number of buckets".
+ * FIRST_VALUE / LAST_VALUE / NTH_VALUE are RESPECT NULLS over the frame [s, f] — f = i (ROWS_TO_CURRENT), f = pe (RANGE_TO_CURRENT),
+ * f = e (PARTITION) — and pick the argument at
+ *   FIRST_VALUE        s
+ *   LAST_VALUE         f
+ *   NTH_VALUE, n > 0   s + n - 1 if that is <= f, otherwise NULL
+ *   NTH_VALUE, n < 0   f + n + 1 if that is >= s, otherwise NULL          (n == 0: "NTH_VALUE needs a non-zero n")
+ * A NULL argument at the picked row gives NULL.  The result has the argument's type (an expression's too) and is nullable: Int32,
+ * Int64, UInt8, UInt32, UInt64, Date32, Float64 (the bits carried unchanged: NaN payloads and -0.0 survive), Decimal128, and
+ * dictionary-encoded strings (the codes are picked, the dictionary handed on).  Boolean and Utf8 arguments are refused ("<FUNC>(<name>)
+ * over <type> is not supported on the GPU path"); no argument: "<FUNC> needs an argument".  LAG / LEAD, GROUPS frames, frames with
+ * offsets and IGNORE NULLS are not taken.
  * DFGPU_WINDOW_TILE = the rows one workgroup takes in the segmented scan behind every function (informative: tests place
  * partitions around its multiples). */
 #define DFGPU_WINDOW_TILE 2048
 typedef enum dfgpu_window_func {
   DFGPU_WINDOW_ROW_NUMBER = 0, DFGPU_WINDOW_RANK = 1, DFGPU_WINDOW_DENSE_RANK = 2,
-  DFGPU_WINDOW_SUM = 3, DFGPU_WINDOW_COUNT = 4, DFGPU_WINDOW_MIN = 5, DFGPU_WINDOW_MAX = 6, DFGPU_WINDOW_AVG = 7
+  DFGPU_WINDOW_SUM = 3, DFGPU_WINDOW_COUNT = 4, DFGPU_WINDOW_MIN = 5, DFGPU_WINDOW_MAX = 6, DFGPU_WINDOW_AVG = 7,
+  DFGPU_WINDOW_PERCENT_RANK = 8, DFGPU_WINDOW_CUME_DIST = 9, DFGPU_WINDOW_NTILE = 10,                  /* ABI 18 */
+  DFGPU_WINDOW_FIRST_VALUE = 11, DFGPU_WINDOW_LAST_VALUE = 12, DFGPU_WINDOW_NTH_VALUE = 13
 } dfgpu_window_func;
 typedef enum dfgpu_window_frame {
   DFGPU_WINDOW_RANGE_TO_CURRENT = 0, /* RANGE BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW */
@@ -706,10 +726,11 @@ typedef enum dfgpu_window_frame {
 } dfgpu_window_frame;
 typedef struct dfgpu_window_spec {
   int32_t func;          /* dfgpu_window_func */
-  int32_t has_arg;       /* 0 = COUNT(*) and the ranking functions */
+  int32_t has_arg;       /* 0 = COUNT(*), the ranking functions and PERCENT_RANK / CUME_DIST / NTILE */
   dfgpu_expr arg;        /* argument expression over the input */
-  int32_t frame;         /* dfgpu_window_frame (aggregate functions) */
+  int32_t frame;         /* dfgpu_window_frame (aggregate and value functions) */
   const char* name;      /* output column name */
+  int64_t n;             /* ABI 18: NTILE's buckets, NTH_VALUE's index; ignored by every other function (a zeroed struct is ABI 17's) */
 } dfgpu_window_spec;
 /* out = the input's columns (zero-copy: the same buffers, dictionaries handed on), then one column per spec, in the input's row
  * order.  Zero rows and zero specs are valid inputs. */

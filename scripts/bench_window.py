@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """WindowAggExec over TPC-H `orders` sorted by (o_custkey, o_orderdate): row_number + rank, a running sum(o_totalprice) over the
-default RANGE frame, and sum over the whole partition — each beside the SortExec below it, from the same run.  Per `window_` launch the
+default RANGE frame, sum over the whole partition, and the functions that take positions from the bitmap words (ntile + percent_rank +
+cume_dist; first_value + last_value over the default frame; nth_value(2) over the ROWS frame) — each beside the SortExec below it, from
+the same run.  Per `window_` launch the
 library recorded (ops.profile_launches): its ms, its algorithmic bytes, and the fraction of the measured copy ceiling (6.29 TB/s, the
 ceiling bench.py and the profiles use) those bytes per that time come to.  Inputs are resident in HBM; one JSON object per line.
 The device generator of `orders` makes no o_totalprice: the column here is CAST(o_orderkey AS Decimal128(15, 2)) — the type and the
@@ -20,7 +22,7 @@ sys.path.insert(0, ROOT)
 HBM_COPY_CEILING_GBS = 6290.0   # bench.py: the measured float4 copy ceiling of the MI355X
 WINDOW_LAUNCHES = ("window_heads", "window_peer_popcount", "window_starts", "window_ends", "window_rank", "window_dense_rank", "window_scan_add_u64",
                    "window_scan_add_i128", "window_scan_add_f64", "window_scan_count", "window_scan_min_i64", "window_scan_max_i64", "window_scan_min_i128",
-                   "window_scan_max_i128", "window_finish", "window_pick")
+                   "window_scan_max_i128", "window_finish", "window_pick", "window_word_starts", "window_word_ends", "window_dist", "window_value")
 
 
 def main():
@@ -53,6 +55,9 @@ def main():
         ("row_number + rank", [("row_number", None, "rn", None), ("rank", None, "rk", None)]),
         ("sum(o_totalprice) range_to_current", [("sum", col("o_totalprice"), "running", "range_to_current")]),
         ("sum(o_totalprice) partition", [("sum", col("o_totalprice"), "total", "partition")]),
+        ("ntile(4) + percent_rank + cume_dist", [(("ntile", 4), None, "q", None), ("percent_rank", None, "pr", None), ("cume_dist", None, "cd", None)]),
+        ("first_value + last_value(o_totalprice) range_to_current", [("first_value", col("o_totalprice"), "first", None), ("last_value", col("o_totalprice"), "last", None)]),
+        ("nth_value(o_totalprice, 2) rows_to_current", [(("nth_value", 2), col("o_totalprice"), "second", "rows_to_current")]),
     ]
     for name, exprs in legs:
         ops.window(sorted_t, ["o_custkey"], ["o_orderdate"], exprs).free()     # warm-up
