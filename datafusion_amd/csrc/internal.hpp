@@ -138,7 +138,7 @@ struct Runtime {
   bool profiling = false;
   struct Rec {
     std::string name;
-    hipEvent_t a, b;
+    hipEvent_t a, b;         // both nullptr: a label (which path ran), collected as one call of 0 ms
     int64_t bytes;
     std::thread::id thread;  // who launched it (dfgpu_metrics.kernel_ns is per thread)
   };
@@ -195,6 +195,14 @@ BufPtr make_zero_buf(size_t bytes);
 
 // scratch helper for small host<->device scalars
 void d2h(void* dst, const void* src, size_t n);  // synchronous w.r.t. the library stream
+// A 4-byte word in pinned host memory that kernels of the calling thread's stream may store to (`dev`) and the host reads (`host`)
+// after hipStreamSynchronize: one per thread and device, never freed.  nullptr: not available (no pinned memory, or
+// `runtime.pinned_readback` off) — the caller keeps a device word and d2h.
+struct HostFlag {
+  volatile unsigned* host = nullptr;
+  unsigned* dev = nullptr;
+};
+HostFlag* thread_host_flag();
 // Pinned host memory from the process-wide pool of the export path (table.hip).  A copy between HBM and PAGEABLE memory beyond a
 // few hundred KB makes the driver pin the caller's pages for the copy; freeing such memory afterwards invalidates a range the kernel
 // driver still tracks, which evicts the process's queues until a worker restores them — measured as 14-23 ms of dead time at the
@@ -261,6 +269,10 @@ struct ColStats {
   bool nondecreasing = false;  // key[i-1] <= key[i] for every row, no NULLs: equal keys are adjacent (ordered input of an aggregate)
   bool has_present = false;    // UInt8 columns, on request (aggregate.hip u8_presence): which of the 256 values occur
   uint64_t present[4] = {0, 0, 0, 0};
+  // join.hip's one-pass rank table build over this (ascending) column: does every workgroup's range of table words fit its LDS
+  // window, so that the build writes every word of the table itself and the table needs no zeroing first?  0: not established;
+  // else bits 63..1 = a tag of the kernel's tiling (a change of its constants makes the answer unknown again), bit 0 = fits.
+  uint64_t onepass_fit = 0;
 };
 
 // Values of a dictionary-encoded column (Arrow Dictionary(index type, Utf8 | LargeUtf8)): the device column holds the

@@ -397,7 +397,8 @@ __global__ __launch_bounds__(BLOCK) void k_rank_setbits(KeyCol k, int64_t n, uin
 // window of RT_WIN words that starts at the workgroup's first word: one LDS OR and one LDS MIN (the run's first row) per run.  The
 // keys of a lane behind its first word change go to the window one by one.  The window then leaves as 16-byte-per-lane stores of
 // consecutive entries.  A key whose word lies beyond the window (a locally sparse stretch of keys) goes to the table directly,
-// which the caller has zeroed: words without a key stay {0, 0} (the contract next to JoinTable::rank_tab).
+// which the caller has zeroed: words without a key stay {0, 0} (the contract next to JoinTable::rank_tab).  A column of which the
+// verifying form has established that no workgroup's words exceed its window is built by the NOFILL form over memory as it comes.
 // VERIFY: min / max / order are the caller's guess; every own row is compared with its predecessor and the guessed range, a
 // violation raises `flag`.  Keys may be anything then: a key outside the range contributes nothing and every store is bounded by
 // the table's size, so a wrong guess leaves a table that is thrown away, never a write outside it.
@@ -426,8 +427,14 @@ constexpr int RT_WIN = 1024;                                        // words sta
 constexpr int RT_LANE_ROWS = 4;                                     // consecutive rows per lane
 constexpr int RT_CHUNK = WAVE * RT_LANE_ROWS;                       // rows per wave and step
 constexpr int RT_STEPS = RT_ROWS / RT_CHUNK / (BLOCK / WAVE);       // steps per wave, all loaded up front
-template <int KT, bool VERIFY>
+// NOFILL: the table is NOT zeroed.  Only for a column whose statistics say that no workgroup's words exceed its window
+// (ColStats::onepass_fit, established by the VERIFY form): the workgroups' ranges [w_first, w_last] then partition [0, n_words) and
+// the window write-out stores every word of it, empty ones as {0, 0}.  The branch beyond the window is compiled out, so this form
+// stores inside its own [w_first, w_first + cnt) and nowhere else, whatever the keys are.
+constexpr uint64_t RT_FIT_TAG = (((uint64_t)RT_ROWS << 32) | (uint64_t)RT_WIN) << 1;   // ColStats::onepass_fit, bits 63..1
+template <int KT, bool VERIFY, bool NOFILL = false>
 __global__ __launch_bounds__(BLOCK) void k_rank_tab_onepass(KeyCol k, int64_t n, uint64_t offset, uint64_t range, ulonglong2* __restrict__ tab, int* __restrict__ flag) {
+  static_assert(!(VERIFY && NOFILL), "a guess is verified over a zeroed table");
   __shared__ unsigned long long s_bits[RT_WIN];
   __shared__ unsigned s_first[RT_WIN];   // first row of the word, relative to the workgroup's first row
   constexpr int WAVES = BLOCK / WAVE;
@@ -463,6 +470,8 @@ __global__ __launch_bounds__(BLOCK) void k_rank_tab_onepass(KeyCol k, int64_t n,
     s_bits[t] = 0ull;
     s_first[t] = ~0u;
   }
+  // (flag bit 1: some workgroup's words exceed its window — what the host remembers as the column's onepass_fit)
+  if (VERIFY && threadIdx.x == 0 && w_end >= w_first && w_end - w_first + 1 > (uint64_t)RT_WIN) atomicOr(flag, 2);
   __syncthreads();
   // one key (or the ORed leading keys of a lane) into its word: `first` = this is the word's first key for certain
   auto put = [&](uint64_t w, unsigned long long bits, int64_t row, bool first_known, bool is_first) {
@@ -470,7 +479,7 @@ __global__ __launch_bounds__(BLOCK) void k_rank_tab_onepass(KeyCol k, int64_t n,
     if (slot < (uint64_t)cnt) {
       atomicOr(&s_bits[slot], bits);   // (a word's keys may sit in two lanes, two steps, two waves)
       atomicMin(&s_first[slot], (unsigned)(row - r0));
-    } else {
+    } else if (!NOFILL) {
       // beyond the window: narrow and scattered, which is what a locally sparse stretch costs; the word's first key is
       // the one whose predecessor row lies in another word
       unsigned long long* e = reinterpret_cast<unsigned long long*>(tab + w);
@@ -1555,15 +1564,17 @@ __global__ __launch_bounds__(BLOCK, ((KIND == KIND_FLAT || KIND == KIND_FLAT16) 
 // Every probe row finds exactly one build row and the output is in probe order: output row i IS probe row i, so the output's
 // probe-side columns are the probe table's own (immutable, reference-counted) columns and only the build-side columns are new.
 // This kernel reads the keys, looks them up, gathers the build payload and writes it at output row = probe row: no tile offsets, so
-// no LDS, no barrier, no cursor — waves are independent.  A row without a partner raises FusedCtl::ticket (the host then starts
+// no LDS, no barrier, no cursor — waves are independent.  A row without a partner raises `miss_flag` (the host then starts
 // over with the counting flavours); rows that did hit still write their own slot only, never outside the np-row allocation.
+// `miss_flag` is the calling thread's word of pinned host memory (thread_host_flag: the host zeroes it before the launch and reads
+// it after the stream has drained — no fill launch in front of the kernel, no copy behind it), else FusedCtl::ticket on the device.
 // cols.n_build == 0 (a RightSemi probe whose every row hits): keys read and verified, nothing written.
 // Measured on the SF100 headline (600 M rows, two 4-byte build columns; profiles/join_shared_probe.md): W = 1 / 2 / 4 / 8 words per
 // wave 3.75 / 2.76 / 2.48 / 2.31 ms; a 4-byte column leaving as one 16-byte store per lane (below) instead of four 4-byte ones
 // 2.31 -> 1.82-1.93 ms: narrow stores are bound by their number, not their bytes; plain against non-temporal stores: no difference.
 constexpr int SHARED_W = 8;  // 64-row words per wave
 template <int KIND, int KT, int W>
-__global__ __launch_bounds__(BLOCK) void k_join_probe_shared(ProbeCtx c, JoinCopyCols cols, int64_t np, FusedCtl* __restrict__ ctl) {
+__global__ __launch_bounds__(BLOCK) void k_join_probe_shared(ProbeCtx c, JoinCopyCols cols, int64_t np, unsigned* __restrict__ miss_flag) {
   static_assert(W % 4 == 0, "4-byte columns leave four words (256 rows) at a time");
   const int64_t n_words = (np + 63) >> 6;
   const unsigned lane = lane_id();
@@ -1575,7 +1586,7 @@ __global__ __launch_bounds__(BLOCK) void k_join_probe_shared(ProbeCtx c, JoinCop
 #pragma unroll
   for (int j = 0; j < W; j++) missed |= (((w0 + j) << 6) + lane) < np && m[j] == 0;
   const uint64_t miss_word = ballot64(missed);
-  if (miss_word && lane == (unsigned)__builtin_ctzll(miss_word)) ctl->ticket = 1u;   // a plain store from one lane: every writer writes the same value
+  if (miss_word && lane == (unsigned)__builtin_ctzll(miss_word)) *miss_flag = 1u;   // a plain store from one lane: every writer writes the same value
   for (int cidx = 0; cidx < cols.n_build; cidx++) {
     const int width = cols.width[cidx];
     if (width == 4) {
@@ -2445,14 +2456,22 @@ static std::unique_ptr<JoinTable> join_build_fixed_keys(const Table& build, cons
     // that wants them (ensure_rank_bits).  Every other build makes bitmap + prefix and leaves the table to ensure_rank_tab.
     BufPtr eager_tab;
     if (ascending && (double)nb >= 0.15 * ((double)range + 1.0)) {
-      eager_tab = make_zero_buf((size_t)n_words * 16);   // words without a key stay {0, 0}
+      // Words without a key stay {0, 0}: the table is zeroed first, unless the column's statistics say that the kernel writes every
+      // word itself (ColStats::onepass_fit, left by the verifying build of this column: no workgroup's words exceed its window)
+      const bool no_fill = known && known->ascending && known->valid == nb && known->onepass_fit == (RT_FIT_TAG | 1ull) && option_on("join.onepass_no_fill", true);
+      eager_tab = no_fill ? make_buf((size_t)n_words * 16) : make_zero_buf((size_t)n_words * 16);
       ProfileScope ps("join_build_rank_tab_onepass", nb * ks.c[0].width + n_words * 16);
       const int g = (int)((nb + RT_ROWS - 1) / RT_ROWS);
       with_key_type(ks.c[0].type, [&](auto kt) {
         constexpr int T = decltype(kt)::value;
         if (speculated) k_rank_tab_onepass<T, true><<<g, BLOCK, 0, r.stream>>>(ks.c[0], nb, (uint64_t)kmin, range, eager_tab->as<ulonglong2>(), need_flag());
+        else if (no_fill) k_rank_tab_onepass<T, false, true><<<g, BLOCK, 0, r.stream>>>(ks.c[0], nb, (uint64_t)kmin, range, eager_tab->as<ulonglong2>(), nullptr);
         else k_rank_tab_onepass<T, false><<<g, BLOCK, 0, r.stream>>>(ks.c[0], nb, (uint64_t)kmin, range, eager_tab->as<ulonglong2>(), nullptr);
       });
+      if (no_fill && r.profiling) {
+        std::lock_guard<std::mutex> lk(r.mu);
+        r.recs.push_back(Runtime::Rec{"join_build_rank_tab_no_fill", nullptr, nullptr, 0, std::this_thread::get_id()});   // (a label: which form ran)
+      }
       DFGPU_HIP(hipGetLastError());
     } else {
     jt->rank_bits = make_zero_buf((size_t)n_words * 8);
@@ -2531,14 +2550,16 @@ static std::unique_ptr<JoinTable> join_build_fixed_keys(const Table& build, cons
     if (speculated) {
       int wrong = 0;
       d2h(&wrong, need_flag(), 4);
-      if (wrong) {  // not ascending after all (or a key outside [first, last]): measure, then build
+      if (wrong & 1) {  // not ascending after all (or a key outside [first, last]): measure, then build
         ProfileScope ps("join_build_speculation_missed", 0);
         jt.reset();
         return join_build_fixed_keys(build, key_cols, null_equality, opts, false);
       }
       // the guess held for every key: first = min, last = max, strictly ascending, no NULLs — the column's statistics from now on
-      std::atomic_store(&const_cast<Column&>(build.cols[key_cols[0]]).stats,
-                        std::make_shared<ColStats>(ColStats{kmin, (long long)((uint64_t)kmin + range), nb, true, true}));
+      // (and, from the one-pass build, whether every workgroup's words fit its window: the next build of this column may skip the fill)
+      ColStats st{kmin, (long long)((uint64_t)kmin + range), nb, true, true};
+      if (eager_tab) st.onepass_fit = RT_FIT_TAG | ((wrong & 2) ? 0ull : 1ull);
+      std::atomic_store(&const_cast<Column&>(build.cols[key_cols[0]]).stats, std::make_shared<ColStats>(st));
     }
     if (!dup) {
       jt->kind = KIND_RANK;
@@ -3257,7 +3278,11 @@ static Table join_probe(JoinTable& jt, const Table& probe, const std::vector<int
     const int invert = join_type == DFGPU_JOIN_RIGHT_ANTI;
     ctx.row_mask = row_mask;
     BufPtr state = fused_mode == FUSED_LOOKBACK ? make_zero_buf((size_t)n_tiles * 8) : nullptr;
-    BufPtr ctl = make_zero_buf(sizeof(FusedCtl));
+    BufPtr ctl;   // (made by the flavour that hands it to a kernel: the shared one reports to the host directly and needs none)
+    auto need_ctl = [&]() {
+      if (!ctl) ctl = make_zero_buf(sizeof(FusedCtl));
+      return ctl->as<FusedCtl>();
+    };
     BufPtr out_words;
     int64_t n_alloc = np;
     // ---- speculation for the probe-order output: a foreign-key probe (every row finds its key) needs no counts pass — row i of
@@ -3321,7 +3346,10 @@ static Table join_probe(JoinTable& jt, const Table& probe, const std::vector<int
         hit_hint->all_hit_hint.store(hit_tag | (speculate ? 1ull : 0ull), std::memory_order_relaxed);
       }
     }
-    if (speculate && share_wanted && !returned_all_hit) {
+    const bool shared_now = speculate && share_wanted && !returned_all_hit;
+    // (every other flavour zeroes its control word here, ahead of its counts pass, as ever: the fill is then not what its kernel waits for)
+    if (!shared_now) need_ctl();
+    if (shared_now) {
       need_tab();   // (a probe `listed` by the guess has not asked for the interleaved rank table yet)
       JoinCopyCols jc{};
       jc.key_col = -1;
@@ -3336,9 +3364,14 @@ static Table join_probe(JoinTable& jt, const Table& probe, const std::vector<int
         jc.n++;
       }
       jc.n_build = jc.n;
-      hipEvent_t ea = nullptr, eb = nullptr, sa = nullptr, sb = nullptr;
+      // where the kernel reports a miss: the thread's word of pinned host memory, zeroed here (the stream is idle with respect to
+      // it: every earlier probe of this thread waited for its kernel); else the device control word, with its fill and its copy
+      HostFlag* box = option_on("join.probe_host_flag", true) ? thread_host_flag() : nullptr;
+      unsigned* miss_flag = box ? box->dev : &need_ctl()->ticket;
+      if (box) *box->host = 0u;
+      hipEvent_t ea = nullptr, eb = nullptr;
       if (r.profiling) {
-        for (hipEvent_t* e : {&ea, &eb, &sa, &sb}) DFGPU_HIP(hipEventCreate(e));
+        for (hipEvent_t* e : {&ea, &eb}) DFGPU_HIP(hipEventCreate(e));
         DFGPU_HIP(hipEventRecord(ea, r.stream));
       }
       with_kind_and_key(kind, ctx.pkeys.c[0].type, [&](auto kd, auto kt) {
@@ -3346,24 +3379,19 @@ static Table join_probe(JoinTable& jt, const Table& probe, const std::vector<int
         if constexpr (K == KIND_RANK || K == KIND_ARRAY || K == KIND_FLAT || K == KIND_FLAT16) {
           const int64_t waves = (n_words + SHARED_W - 1) / SHARED_W;
           const unsigned g = (unsigned)((waves + BLOCK / WAVE - 1) / (BLOCK / WAVE));
-          k_join_probe_shared<K, T, SHARED_W><<<g, BLOCK, 0, r.stream>>>(ctx, jc, np, ctl->as<FusedCtl>());
+          k_join_probe_shared<K, T, SHARED_W><<<g, BLOCK, 0, r.stream>>>(ctx, jc, np, miss_flag);
         }
       });
       DFGPU_HIP(hipGetLastError());
-      if (r.profiling) {
-        DFGPU_HIP(hipEventRecord(eb, r.stream));
-        DFGPU_HIP(hipEventRecord(sa, r.stream));
-        DFGPU_HIP(hipEventRecord(sb, r.stream));
-      }
+      if (r.profiling) DFGPU_HIP(hipEventRecord(eb, r.stream));
       unsigned missed = 0;   // the one read-back: the output's row count is np without asking
-      d2h(&missed, &ctl->as<FusedCtl>()->ticket, 4);
-      if (missed) {
-        if (r.profiling) {
-          DFGPU_HIP(hipEventDestroy(sa));
-          DFGPU_HIP(hipEventDestroy(sb));
-        }
-        return probe_again_counted(ea, eb);
+      if (box) {
+        DFGPU_HIP(hipStreamSynchronize(r.stream));
+        missed = *box->host;
+      } else {
+        d2h(&missed, miss_flag, 4);
       }
+      if (missed) return probe_again_counted(ea, eb);
       for (int c : pout) {   // second owners of the probe's buffers; the rows are the same rows, so the statistics stay
         out.cols.push_back(probe.cols[c]);
         out.cols.back().length = np;
@@ -3371,7 +3399,7 @@ static Table join_probe(JoinTable& jt, const Table& probe, const std::vector<int
       if (r.profiling) {
         std::lock_guard<std::mutex> lk(r.mu);
         r.recs.push_back(Runtime::Rec{want_single ? "join_probe_fused" : "join_probe_placed", ea, eb, bytes, std::this_thread::get_id()});
-        r.recs.push_back(Runtime::Rec{"join_probe_shared_columns", sa, sb, 0, std::this_thread::get_id()});   // (which path ran; moves nothing)
+        r.recs.push_back(Runtime::Rec{"join_probe_shared_columns", nullptr, nullptr, 0, std::this_thread::get_id()});   // (a label: which path ran; moves nothing)
       }
       out.nrows = np;
       jt.info.output_rows += out.nrows;
@@ -3459,7 +3487,8 @@ static Table join_probe(JoinTable& jt, const Table& probe, const std::vector<int
       // look-back: persistent workgroups pulling tickets; unordered / placed: one workgroup per tile
       const unsigned g = fused_mode == FUSED_LOOKBACK ? (unsigned)std::min<int64_t>(n_tiles, (int64_t)r.num_cus * 8) : (unsigned)n_tiles;
       uint64_t* st = state ? state->as<uint64_t>() : nullptr;
-      auto launch = [&](auto kern) { kern<<<g, BLOCK, 0, r.stream>>>(ctx, jc, np, invert, st, ctl->as<FusedCtl>(), row_mask); };
+      FusedCtl* const d_ctl = need_ctl();
+      auto launch = [&](auto kern) { kern<<<g, BLOCK, 0, r.stream>>>(ctx, jc, np, invert, st, d_ctl, row_mask); };
       with_kind_and_key(kind, ctx.pkeys.c[0].type, [&](auto kd, auto kt) {
         constexpr int K = decltype(kd)::value, T = decltype(kt)::value;
         constexpr bool KR = kind_is_direct<K>();  // the direct-address kinds hold the one integer key in registers
@@ -3488,10 +3517,10 @@ static Table join_probe(JoinTable& jt, const Table& probe, const std::vector<int
       });
       DFGPU_HIP(hipGetLastError());
       if (r.profiling) DFGPU_HIP(hipEventRecord(eb, r.stream));
-      if (fused_mode != FUSED_PLACED) n_out = (int64_t)read_u64(reinterpret_cast<const uint64_t*>(&ctl->as<FusedCtl>()->total));
+      if (fused_mode != FUSED_PLACED) n_out = (int64_t)read_u64(reinterpret_cast<const uint64_t*>(&d_ctl->total));
       if (speculate) {
         unsigned missed = 0;
-        d2h(&missed, &ctl->as<FusedCtl>()->ticket, 4);
+        d2h(&missed, &d_ctl->ticket, 4);
         if (missed) return probe_again_counted(ea, eb);   // some probe row has no partner after all
       }
     } else if (r.profiling) {

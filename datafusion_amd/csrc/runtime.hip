@@ -327,6 +327,34 @@ void d2h(void* dst, const void* src, size_t n) {
   DFGPU_HIP(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, rt().stream));
   DFGPU_HIP(hipStreamSynchronize(rt().stream));
 }
+// A flag that a kernel raises for the host alone (the shared probe's "some row has no partner") needs neither a device word that is
+// zeroed before the launch nor a copy after it: the kernel stores into pinned host memory and the host reads the word once the
+// stream has drained.  One word per calling thread and device, never freed (as t_pin above); a thread's stream is idle with respect to
+// its word between two uses, because every user waits for its kernel before it reads.
+HostFlag* thread_host_flag() {
+  if (!option_on("runtime.pinned_readback", true)) return nullptr;
+  struct Slot { HostFlag f; bool failed = false; };
+  static thread_local std::vector<Slot> t_flags;   // indexed by device id
+  const int d = rt().device;
+  if (d < 0) return nullptr;
+  if ((int)t_flags.size() <= d) t_flags.resize((size_t)d + 1);
+  Slot& s = t_flags[(size_t)d];
+  if (s.failed) return nullptr;
+  if (!s.f.host) {
+    void* h = nullptr;
+    void* dev = nullptr;
+    if (hipHostMalloc(&h, 64, hipHostMallocDefault) != hipSuccess || hipHostGetDevicePointer(&dev, h, 0) != hipSuccess || !dev) {
+      (void)hipGetLastError();
+      if (h) (void)hipHostFree(h);
+      s.failed = true;   // (the callers keep their device word and its copy)
+      return nullptr;
+    }
+    s.f.host = static_cast<volatile unsigned*>(h);
+    s.f.dev = static_cast<unsigned*>(dev);
+    *s.f.host = 0u;
+  }
+  return &s.f;
+}
 void h2d_async(void* dst, const void* src, size_t n) {
   DFGPU_HIP(hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, rt().stream));
 }
@@ -363,9 +391,11 @@ void Runtime::collect() {
   (void)hipDeviceSynchronize();   // the events were recorded on their threads' streams
   for (auto& rec : recs) {
     float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, rec.a, rec.b);
-    (void)hipEventDestroy(rec.a);
-    (void)hipEventDestroy(rec.b);
+    if (rec.a) {   // (a label has no events: one call, 0 ms)
+      (void)hipEventElapsedTime(&ms, rec.a, rec.b);
+      (void)hipEventDestroy(rec.a);
+      (void)hipEventDestroy(rec.b);
+    }
     auto it = std::find_if(stats.begin(), stats.end(), [&](const dfgpu_kernel_stat& s) { return rec.name == s.name; });
     if (it == stats.end()) {
       dfgpu_kernel_stat s{};

@@ -482,7 +482,9 @@ int dfgpu_join_estimate_bytes(int64_t build_rows, int64_t build_row_bytes, int64
  * probe row matches exactly one build row and the output is in probe order (a foreign-key probe: Inner over unique build
  * keys, RightSemi), the probe-side output columns are second owners of the probe table's columns and only the build-side
  * columns are written.  Tables are immutable and their buffers reference-counted, so either table may be freed first.
- * Options (dfgpu_set_option): join.share_probe, join.share_probe_min_rows. */
+ * Options (dfgpu_set_option): join.share_probe, join.share_probe_min_rows; join.probe_host_flag (off: that probe reports a row
+ * without a partner through a device word and a copy instead of a word of pinned host memory), join.onepass_no_fill (off:
+ * dfgpu_join_build always zeroes the rank table of ascending keys first). */
 int dfgpu_join_probe(dfgpu_join_t ht, dfgpu_table_t probe, const int* probe_key_cols, int join_type,
                      const int* build_out_cols, int n_build_out, const int* probe_out_cols, int n_probe_out,
                      dfgpu_table_t* out);
