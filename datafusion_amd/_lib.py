@@ -126,6 +126,7 @@ SYMBOLS = [
     "dfgpu_table_retain", "dfgpu_table_export_device", "dfgpu_table_import_device",
     "dfgpu_cache_create", "dfgpu_cache_free", "dfgpu_cache_get", "dfgpu_cache_put", "dfgpu_cache_clear", "dfgpu_cache_get_stats", "dfgpu_jit_cache_stats", "dfgpu_join_contains", "dfgpu_exchange_join_visited", "dfgpu_exchange_range",
     "dfgpu_agg_create_grouping_sets", "dfgpu_ipc_open", "dfgpu_ipc_close", "dfgpu_ipc_info", "dfgpu_ipc_column", "dfgpu_ipc_batch_rows", "dfgpu_ipc_read_batch",
+    "dfgpu_nested_loop_join",
 ]
 
 _lib = None

@@ -193,6 +193,11 @@ using BufPtr = std::shared_ptr<DevBuf>;
 inline BufPtr make_buf(size_t bytes) { return std::make_shared<DevBuf>(bytes ? bytes : 1); }
 BufPtr make_zero_buf(size_t bytes);
 
+// admission against the pool's limit (dfgpu_mem_set_limit; runtime.hip): throws the "Resources exhausted" error of
+// dfgpu_mem_try_reserve when `bytes` more cannot be admitted; reserves nothing
+void pool_admit(int64_t bytes);
+int64_t pool_free_bytes();  // limit - bytes in use - bytes reserved (never negative)
+
 // scratch helper for small host<->device scalars
 void d2h(void* dst, const void* src, size_t n);  // synchronous w.r.t. the library stream
 // A 4-byte word in pinned host memory that kernels of the calling thread's stream may store to (`dev`) and the host reads (`host`)
@@ -435,6 +440,17 @@ ColStats column_stats(Column& c, int64_t nrows);
 // ----------------------------------------------------------------- visited marks of a replicated build side (join.hip)
 std::vector<uint8_t> join_visited_export(dfgpu_join_t h);                       // one bit per build row + 8 bytes of null-aware flags
 void join_visited_merge(dfgpu_join_t h, const uint8_t* merged, size_t nbytes);  // OR into the table's marks
+
+// ----------------------------------------------------------------- the tail of a filtered join (join.hip), shared with nlj.hip
+// passing pairs + per-row match bytes -> a join type's rows: the pieces join_probe_with_filter and dfgpu_join_emit_unmatched are made of
+// mask bit i = (bytes[i] != 0) == want_set, for i < n (k_visited_mask)
+void join_bytes_mask(const uint8_t* bytes, int64_t n, bool want_set, uint64_t* mask);
+// row ids of `mask`'s set bits -> row_side[base + rank], null_side[base + rank] = -1 (k_append_unmatched)
+void join_append_unmatched(const uint64_t* mask, const uint64_t* prefix, int64_t n, int64_t base, int64_t* null_side, int64_t* row_side);
+// the pairs whose `pass` bit is set, order kept (k_pairs_compact; prefix = scan_mask_popcounts of pass)
+void join_pairs_compact(const int64_t* ob, const int64_t* op, const uint64_t* pass, const uint64_t* prefix, int64_t m, int64_t* ob2, int64_t* op2);
+// the non-null Boolean `mark` column of the Mark join types from one byte per row
+Column mark_column(const uint8_t* bytes, int64_t n);
 
 // ----------------------------------------------------------------- radix passes (sort.hip)
 // (key u64, row id u32) pairs stably sorted by bits [lo_bit, lo_bit + nbits) of the key; `idx` null on entry = row id is the position

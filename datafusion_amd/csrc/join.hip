@@ -2224,7 +2224,7 @@ static ProbeCtx make_ctx(JoinTable& jt, const Table& probe, const std::vector<in
   return c;
 }
 
-static Column mark_column(const uint8_t* bytes, int64_t n) {
+Column mark_column(const uint8_t* bytes, int64_t n) {
   dfgpu_field f{};
   f.type = DFGPU_BOOL;
   Column c = alloc_column(f, "mark", n);
@@ -3748,6 +3748,20 @@ static Pairs key_equal_pairs(JoinTable& jt, const Table& probe, const std::vecto
   });
   DFGPU_HIP(hipGetLastError());
   return P;
+}
+
+// the tail's kernels for nlj.hip (internal.hpp)
+void join_bytes_mask(const uint8_t* bytes, int64_t n, bool want_set, uint64_t* mask) {
+  if (n) k_visited_mask<<<grid_for((n + 63) / 64, BLOCK / WAVE), BLOCK, 0, rt().stream>>>(bytes, n, want_set ? 1 : 0, mask);
+  DFGPU_HIP(hipGetLastError());
+}
+void join_append_unmatched(const uint64_t* mask, const uint64_t* prefix, int64_t n, int64_t base, int64_t* null_side, int64_t* row_side) {
+  if (n) k_append_unmatched<<<grid_for((n + 63) / 64, BLOCK / WAVE), BLOCK, 0, rt().stream>>>(mask, prefix, n, base, null_side, row_side);
+  DFGPU_HIP(hipGetLastError());
+}
+void join_pairs_compact(const int64_t* ob, const int64_t* op, const uint64_t* pass, const uint64_t* prefix, int64_t m, int64_t* ob2, int64_t* op2) {
+  if (m) k_pairs_compact<<<grid_for((m + 63) / 64, BLOCK / WAVE), BLOCK, 0, rt().stream>>>(ob, op, pass, prefix, m, ob2, op2);
+  DFGPU_HIP(hipGetLastError());
 }
 
 // pairs -> [JoinFilter] -> the join type's output (apply_join_filter_to_indices + adjust_indices_by_join_type, joins/utils.rs:1248-1318,1432-1488)

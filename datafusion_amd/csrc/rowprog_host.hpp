@@ -59,6 +59,8 @@ class RowProgramCompiler {
   int keep_output_if(int out, const dfgpu_expr& filter, const std::string& what);
   // false (with a reason) when the forest does not fit: too many columns / registers / instructions
   bool finish(CompiledProgram& cp, std::string& why);
+  // column slot (= register, = index into RowProgram::col_data) -> column of the input table, in the order the forest first reads them
+  const std::vector<int>& slot_columns() const { return slot_col_; }
 
  private:
   struct Val {

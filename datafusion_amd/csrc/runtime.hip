@@ -627,6 +627,30 @@ int64_t limit_of(int device) {
 }
 }  // namespace
 
+extern "C++" {
+namespace dfgpu {
+static int64_t pool_in_use(Runtime& r) {
+  std::lock_guard<std::mutex> lk(r.mu);
+  return r.in_use;
+}
+void pool_admit(int64_t bytes) {
+  Runtime& r = rt();
+  const int64_t in_use = pool_in_use(r);
+  std::lock_guard<std::mutex> lk(g_res_mu);
+  const int64_t lim = limit_of(r.device), held = g_reserved[r.device];
+  if (in_use + held + bytes > lim)
+    throw Error("Resources exhausted: Failed to allocate additional " + std::to_string(bytes) + " bytes of HBM with " + std::to_string(in_use) +
+                " bytes in tables and " + std::to_string(held) + " bytes already reserved - maximum available is " + std::to_string(lim));
+}
+int64_t pool_free_bytes() {
+  Runtime& r = rt();
+  const int64_t in_use = pool_in_use(r);
+  std::lock_guard<std::mutex> lk(g_res_mu);
+  return std::max<int64_t>(0, limit_of(r.device) - in_use - g_reserved[r.device]);
+}
+}  // namespace dfgpu
+}  // extern "C++"
+
 int dfgpu_mem_set_limit(int64_t bytes) {
   return guarded([&] {
     require_init();

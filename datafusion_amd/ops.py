@@ -212,6 +212,37 @@ def hash_join(left: DeviceTable, right: DeviceTable, on, join_type="Inner", null
     return out
 
 
+def lower_join_filter(left, right, join_filter):
+    """JoinFilter (expression over f0, f1, ..., [(column index, "Left" | "Right"), ...]) -> (the C struct, what it points at).  String
+    literals compared with intermediate columns are bound through the dictionaries of the columns behind them, as in JoinHashTable.probe."""
+    from .expr import IntermediateSchema, _has_string_literal
+    fexpr, fcols = join_filter
+    view = IntermediateSchema(left, right, fcols) if _has_string_literal(fexpr) else None
+    le = lower(fexpr, [f"f{i}" for i in range(len(fcols))], view)
+    idx = (C.c_int32 * max(1, len(fcols)))(*[int(i) for i, _ in fcols])
+    side = (C.c_int32 * max(1, len(fcols)))(*[0 if sd == "Left" else 1 for _, sd in fcols])
+    return JoinFilter(le.c, idx, side, len(fcols)), (le, idx, side)
+
+
+def nested_loop_join(left: DeviceTable, right: DeviceTable, join_type="Inner", join_filter=None, left_cols=None, right_cols=None) -> DeviceTable:
+    """NestedLoopJoinExec over whole tables (dfgpu_nested_loop_join): left = the collected side, right = the probe side; `join_filter` as in
+    JoinHashTable.probe, None = every pair matches (CrossJoinExec for "Inner").  The whole result in one table, in the order of
+    hash_join with the same filter: passing pairs right-row-major, unmatched right rows, unmatched left rows."""
+    lib = _lib.init()
+    lc = list(range(left.num_columns)) if left_cols is None else [left.index_of(c) for c in left_cols]
+    rc = list(range(right.num_columns)) if right_cols is None else [right.index_of(c) for c in right_cols]
+    if join_type in ("LeftSemi", "LeftAnti", "LeftMark"):
+        rc = []
+    if join_type in ("RightSemi", "RightAnti", "RightMark"):
+        lc = []
+    jf, keep = (None, None) if join_filter is None else lower_join_filter(left, right, join_filter)
+    out = C.c_void_p()
+    check(lib.dfgpu_nested_loop_join(left.handle, right.handle, JOIN_TYPES[join_type], None if jf is None else C.byref(jf), _ints(lc), len(lc),
+                                     _ints(rc), len(rc), C.byref(out)))
+    del keep
+    return DeviceTable(out)
+
+
 def tail_probe_schema(right: DeviceTable, join_type, probe_cols=None):
     """the NULL-filled probe columns of the unmatched build rows of Left / Full joins (dfgpu_join_emit_unmatched's probe_fields)"""
     if join_type not in ("Left", "Full"):

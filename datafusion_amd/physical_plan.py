@@ -18,6 +18,7 @@ per-operator GPU node):
   RepartitionExec(Hash) on one GPU                   -> removed                 (one partition per GPU)
   SortPreservingMergeExec on one GPU                 -> removed                 (one sorted partition is the merge)
 WindowAggExec stays the node it is (dfgpu_window); the rule demands order of its child, so the SortExec below keeps its meaning.
+NestedLoopJoinExec / CrossJoinExec stay the nodes they are (dfgpu_nested_loop_join); only their right child inherits the parent's need of order.
 """
 from __future__ import annotations
 
@@ -446,6 +447,52 @@ class HashJoinExec(ExecutionPlan):
             (", null_aware" if self.null_aware else "")
 
 
+class NestedLoopJoinExec(ExecutionPlan):
+    """NestedLoopJoinExec::try_new(left = the collected side, right = the probe side, filter, join_type, projection)
+    (joins/nested_loop_join.rs): the join of a condition without an equality.  `filter` = JoinFilter as in HashJoinExec (expression over
+    f0, f1, ..., [(column index, "Left" | "Right"), ...]); None = every pair matches.  `projection` = (left columns, right columns).
+    Output order: ops.nested_loop_join's (the filtered hash join's)."""
+
+    def __init__(self, left: ExecutionPlan, right: ExecutionPlan, filter=None, join_type="Inner", projection=None):
+        if join_type not in ops.JOIN_TYPES:
+            raise ValueError(f"unknown join type {join_type!r}")
+        self.left, self.right, self.filter, self.join_type, self.projection = left, right, filter, join_type, projection
+
+    def children(self):
+        return [self.left, self.right]
+
+    def with_new_children(self, c):
+        return NestedLoopJoinExec(c[0], c[1], self.filter, self.join_type, self.projection)
+
+    def execute(self, partition=0):
+        l, lo = self._run_child(self.left)
+        r, ro = self._run_child(self.right)
+        lc, rc = self.projection if self.projection else (None, None)
+        try:
+            return ops.nested_loop_join(l, r, self.join_type, self.filter, lc, rc)
+        finally:
+            for t, o in ((l, lo), (r, ro)):
+                if o:
+                    t.free()
+
+    def detail(self):
+        return f"join_type={self.join_type}" + (f", filter={self.filter[0]!r}" if self.filter is not None else "") + \
+            (f", projection={self.projection}" if self.projection else "")
+
+
+class CrossJoinExec(NestedLoopJoinExec):
+    """CrossJoinExec::new(left, right) (joins/cross_join.rs): every pair — the inner nested-loop join without a filter"""
+
+    def __init__(self, left: ExecutionPlan, right: ExecutionPlan):
+        super().__init__(left, right, None, "Inner", None)
+
+    def with_new_children(self, c):
+        return CrossJoinExec(c[0], c[1])
+
+    def detail(self):
+        return ""
+
+
 def replicated_build(node: ExecutionPlan) -> bool:
     """several ranks and the build side is a CoalescePartitionsExec (every rank holds ALL build rows: PartitionMode::CollectLeft)"""
     from .queries import _world
@@ -663,6 +710,23 @@ class GpuOffloadRule:
             self.declined.append((node, str(e)))
             return False
 
+    def _admits_pairs(self, node) -> bool:
+        """a pair-output nested-loop join without a filter (a cross join) is the one join whose output size is known at plan time:
+        |L| x |R| rows of 16 bytes of row ids (plus the rows themselves).  One the pool cannot reserve stays the reference's operator."""
+        if node.filter is not None or node.join_type not in ("Inner", "Left", "Right", "Full") or _lib._initialised_device is None:
+            return True
+        try:
+            l_rows, l_bytes = _row_bound(node.left)
+            r_rows, r_bytes = _row_bound(node.right)
+        except (TypeError, AttributeError):
+            return True
+        try:
+            ops.Reservation(l_rows * r_rows * (16 + l_bytes + r_bytes)).release()
+            return True
+        except _lib.DfgpuError as e:
+            self.declined.append((node, str(e)))
+            return False
+
     def name(self) -> str:
         return "gpu_offload_amd"
 
@@ -681,7 +745,7 @@ class GpuOffloadRule:
                 need = False                                   # these consume their input in any order
             elif isinstance(node, WindowAggExec):
                 need = True                                    # partitions and peer groups ARE the input's order, whatever the parent needs
-            elif isinstance(node, HashJoinExec):
+            elif isinstance(node, (HashJoinExec, NestedLoopJoinExec)):
                 need = parent_needs_order and i == 1           # only the probe side's order shows in the output
             else:
                 need = parent_needs_order                      # FilterExec / ProjectionExec / CoalesceBatchesExec keep it
@@ -698,6 +762,11 @@ class GpuOffloadRule:
             node.kept_on_cpu = True
             self.declined.append((node, f"WindowAggExec on {self.world_size} ranks: the window is only exercised on one rank"))
             return node
+        if isinstance(node, NestedLoopJoinExec) and self.world_size > 1 and not getattr(node, "kept_on_cpu", False):
+            # every rank would need the whole left side and a share of the right one: that path is not exercised, so the node is not taken
+            node.kept_on_cpu = True
+            self.declined.append((node, f"{node.name()} on {self.world_size} ranks: the nested loop join is only exercised on one rank"))
+            return node
         if not isinstance(node, (GpuHashJoinExec, GpuFusedAggregateExec)) and not getattr(node, "kept_on_cpu", False):
             try:
                 reason = unsupported_reason(node)
@@ -708,6 +777,9 @@ class GpuOffloadRule:
                 self.declined.append((node, reason))
                 return node
         if isinstance(node, HashJoinExec) and not isinstance(node, GpuHashJoinExec) and not self._admits(node):
+            node.kept_on_cpu = True
+            return node
+        if isinstance(node, NestedLoopJoinExec) and not getattr(node, "kept_on_cpu", False) and not self._admits_pairs(node):
             node.kept_on_cpu = True
             return node
         if isinstance(node, HashJoinExec) and not isinstance(node, GpuHashJoinExec):
@@ -753,6 +825,13 @@ def _row_bound(node):
     if isinstance(node, HashJoinExec):
         (br, bb), (pr, pb) = _row_bound(node.left), _row_bound(node.right)
         return max(br, pr), bb + pb
+    if isinstance(node, NestedLoopJoinExec):
+        (br, bb), (pr, pb) = _row_bound(node.left), _row_bound(node.right)
+        if node.join_type in ("LeftSemi", "LeftAnti", "LeftMark"):
+            return br, bb + 1
+        if node.join_type in ("RightSemi", "RightAnti", "RightMark"):
+            return pr, pb + 1
+        return br * pr + br + pr, bb + pb
     raise TypeError(node.name())
 
 
@@ -784,6 +863,28 @@ def plan_schema(node):
             return pa.schema(lf + [pa.field("mark", pa.bool_())])
         if jt == "RightMark":
             return pa.schema(rf + [pa.field("mark", pa.bool_())])
+        return pa.schema(lf + rf)
+    if isinstance(node, NestedLoopJoinExec):
+        l, r = plan_schema(node.left), plan_schema(node.right)
+        if l is None or r is None:
+            return None
+        lc, rc = node.projection if node.projection is not None else (None, None)
+        lf = list(l) if lc is None else [l.field(l.get_field_index(c)) if isinstance(c, str) else l.field(c) for c in lc]
+        rf = list(r) if rc is None else [r.field(r.get_field_index(c)) if isinstance(c, str) else r.field(c) for c in rc]
+        jt = node.join_type
+        if jt in ("LeftSemi", "LeftAnti"):
+            return pa.schema(lf)
+        if jt in ("RightSemi", "RightAnti"):
+            return pa.schema(rf)
+        if jt == "LeftMark":
+            return pa.schema(lf + [pa.field("mark", pa.bool_(), nullable=False)])
+        if jt == "RightMark":
+            return pa.schema(rf + [pa.field("mark", pa.bool_(), nullable=False)])
+        # build_join_schema (joins/utils.rs): the side that unmatched rows of the other side extend with NULLs becomes nullable
+        if jt in ("Right", "Full"):
+            lf = [f.with_nullable(True) for f in lf]
+        if jt in ("Left", "Full"):
+            rf = [f.with_nullable(True) for f in rf]
         return pa.schema(lf + rf)
     kids = node.children()
     if len(kids) != 1:
@@ -1000,6 +1101,34 @@ def unsupported_reason(node):
         bits = sum(_key_bits(inp.field(inp.get_field_index(c) if isinstance(c, str) else c).type) for c, _, _ in node.expr)
         if bits > 192:   # sort.hip: "packed sort key longer than 192 bits"
             return f"sort key of up to {bits} bits: the device packs at most 192"
+        return None
+    if isinstance(node, NestedLoopJoinExec):
+        if node.filter is None:
+            return None
+        l, r = plan_schema(node.left), plan_schema(node.right)
+        if l is None or r is None:
+            return None
+        fexpr, fcols = node.filter
+        try:
+            inter = pa.schema([pa.field(f"f{k}", (l if side == "Left" else r).field(int(i)).type) for k, (i, side) in enumerate(fcols)])
+        except (KeyError, IndexError, ValueError) as err:
+            return f"join filter column index out of range: {err}"
+        try:
+            empty = DeviceTable.from_arrow(inter.empty_table())
+        except Exception:  # noqa: BLE001
+            return None
+        try:
+            # nlj.hip nested_loop_join: "join filter expression must be Boolean"; a filter the expression layer cannot lower stays here too
+            try:
+                ft = ops.expr_type(empty, fexpr)
+            except _lib.DfgpuError as err:
+                return f"join filter {fexpr!r}: {err}"
+            except (KeyError, TypeError, ValueError) as err:
+                return f"join filter {fexpr!r} cannot be lowered: {err}"
+            if not pa.types.is_boolean(ft):
+                return f"join filter expression must be Boolean: {fexpr!r} is {ft}"
+        finally:
+            empty.free()
         return None
     if isinstance(node, HashJoinExec):
         try:

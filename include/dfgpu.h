@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define DFGPU_ABI_VERSION 18
+#define DFGPU_ABI_VERSION 19
 
 /* Arrow C Data Interface (https://arrow.apache.org/docs/format/CDataInterface.html) */
 #ifndef ARROW_C_DATA_INTERFACE
@@ -512,6 +512,21 @@ typedef struct dfgpu_join_filter {
 } dfgpu_join_filter;
 int dfgpu_join_probe_with_filter(dfgpu_join_t ht, dfgpu_table_t probe, const int* probe_key_cols, int join_type, const dfgpu_join_filter* filter,
                                  const int* build_out_cols, int n_build_out, const int* probe_out_cols, int n_probe_out, dfgpu_table_t* out);
+
+/* ABI 19 — NestedLoopJoinExec (joins/nested_loop_join.rs) over whole tables: left = the collected (build) side, right = the probe side.
+ * filter == NULL: every pair passes (CrossJoinExec for DFGPU_JOIN_INNER).  A pair matches when the filter's value is TRUE; FALSE and
+ * NULL are not matches.  One call returns the whole result, the unmatched left rows included: there is no handle.  All ten join
+ * types; output columns are left_out_cols of `left`, then right_out_cols of `right` (Left/Right Semi / Anti: their side only; the
+ * Mark types append the non-null Boolean `mark` column; the NULL-extended side of Left / Right / Full becomes nullable).
+ * Output order (the layout of the filtered hash join: dfgpu_join_probe_with_filter, then dfgpu_join_emit_unmatched):
+ *   Inner / Left / Right / Full: the passing pairs in right-row-major order (ascending right row, ascending left row within one right
+ *     row), then the unmatched right rows, ascending (Right / Full), then the unmatched left rows, ascending (Left / Full);
+ *   RightSemi / RightAnti / RightMark: right-row order;  LeftSemi / LeftAnti / LeftMark: left-row order.
+ * The pair-output types count first and allocate exactly; an output the pool's limit does not admit fails with "Resources exhausted"
+ * before a pair is written.  Options: nlj.rowprog (0 = always the materialising path), nlj.left_chunk_rows, nlj.chunk_pairs,
+ * nlj.early_exit (0 = derived / on). */
+int dfgpu_nested_loop_join(dfgpu_table_t left, dfgpu_table_t right, int join_type, const dfgpu_join_filter* filter,
+                           const int* left_out_cols, int n_left_out, const int* right_out_cols, int n_right_out, dfgpu_table_t* out);
 
 /* min / max / non-null count of an integer column and whether it is strictly ascending (the statistics
  * ArrayMap::try_new takes from the build keys, joins/array_map.rs:175-203; also the probe-key bounds the multi-GPU
