@@ -2571,7 +2571,7 @@ static std::unique_ptr<JoinTable> join_build_fixed_keys(const Table& build, cons
       jt->info.table_bytes = n_words * 16;
       jt->rank_tab = eager_tab;
     } else {
-      DFGPU_CHECK(opts.table_mode != 3, "rank-map join table requested but the build keys are not unique");
+      DFGPU_CHECK(opts.table_mode != 3, "rank-map join table requested but not applicable: the build keys are not unique");
       jt->rank_bits.reset();
       jt->rank_prefix.reset();
     }

@@ -1026,15 +1026,22 @@ int dfgpu_table_concat(const dfgpu_table_t* parts, int nparts, dfgpu_table_t* ou
       std::shared_ptr<DictValues> merged;
       std::map<std::string, int32_t> merged_index;
       std::vector<BufPtr> keep;
+      // a part without a dictionary that holds no value — no row, or NULL in every row: the NULL-filled probe columns behind the
+      // unmatched build rows of a Left / Full join, made from the column's type alone — goes with any dictionary
+      auto holds_no_value = [](const Table* t, const Column& c) { return !c.dict && (t->nrows == 0 || (c.validity && c.null_count == t->nrows)); };
       if (fc.dict) {
         bool same = true;
         for (int p = 0; p < nparts; p++) {
-          const auto& d = unwrap(parts[p])->cols[ci].dict;
+          const Table* t = unwrap(parts[p]);
+          const auto& d = t->cols[ci].dict;
+          if (holds_no_value(t, t->cols[ci])) continue;
           same &= d == fc.dict || (d && d->values == fc.dict->values && d->valid == fc.dict->valid);
         }
         if (!same) {
           for (int p = 0; p < nparts; p++) {
-            const auto& d = unwrap(parts[p])->cols[ci].dict;
+            const Table* t = unwrap(parts[p]);
+            const auto& d = t->cols[ci].dict;
+            if (holds_no_value(t, t->cols[ci])) continue;
             DFGPU_CHECK(d != nullptr, "concat: dictionary-encoded and plain columns mixed");
             for (size_t k = 0; k < d->values.size(); k++) merged_index.emplace(d->valid[k] ? d->values[k] : std::string("\0null", 5), 0);
           }
@@ -1059,8 +1066,11 @@ int dfgpu_table_concat(const dfgpu_table_t* parts, int nparts, dfgpu_table_t* ou
         Table* t = unwrap(parts[p]);
         const Column& c = t->cols[ci];
         DFGPU_CHECK(c.field.type == fc.field.type, "concat: column type mismatch");
-        DFGPU_CHECK((c.dict != nullptr) == (fc.dict != nullptr), "concat: dictionary-encoded and plain columns mixed");
-        if (merged && t->nrows) {
+        const bool no_value = fc.dict && holds_no_value(t, c);
+        DFGPU_CHECK(no_value || (c.dict != nullptr) == (fc.dict != nullptr), "concat: dictionary-encoded and plain columns mixed");
+        if (merged && t->nrows && no_value) {   // NULL in every row: index 0 under every NULL
+          DFGPU_HIP(hipMemsetAsync((char*)n.data->ptr + (size_t)off * w, 0, (size_t)t->nrows * w, rt().stream));
+        } else if (merged && t->nrows) {
           // this part's indices -> indices of the merged dictionary
           std::vector<int32_t> remap(c.dict->values.size(), 0);
           for (size_t k = 0; k < remap.size(); k++) remap[k] = merged_index.at(c.dict->valid[k] ? c.dict->values[k] : std::string("\0null", 5));
