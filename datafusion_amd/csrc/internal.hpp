@@ -167,6 +167,18 @@ struct ProfileScope {
   ProfileScope(const char* name, int64_t algorithmic_bytes);
   ~ProfileScope();
 };
+// Its sibling for a launch whose algorithmic bytes — or whose name — are known only after it: begins like a ProfileScope, stop()
+// marks the end of the launch, record() files it.  Events that are never filed are destroyed.  (No thread metrics: bytes come late.)
+struct LateRecord {
+  hipEvent_t a = nullptr, b = nullptr;
+  LateRecord();
+  ~LateRecord();
+  LateRecord(const LateRecord&) = delete;
+  LateRecord& operator=(const LateRecord&) = delete;
+  void stop();
+  void record(const char* name, int64_t algorithmic_bytes);
+  static void label(const char* name);   // a record without events: which path ran; moves nothing
+};
 
 // Refcounted device buffer from the pool.
 struct DevBuf {

@@ -3024,162 +3024,114 @@ struct LazyRowFilter {
   int64_t pred_bytes_per_row;
   std::function<const uint64_t*()> mask;
 };
-static Table join_probe(JoinTable& jt, const Table& probe, const std::vector<int>& pk, int join_type, const std::vector<int>& bout_in,
-                        const std::vector<int>& pout, const uint64_t* row_mask = nullptr, bool* mask_consumed = nullptr, const LazyRowFilter* lazy = nullptr) {
-  Runtime& r = rt();
-  if (row_mask) lazy = nullptr;
-  auto need_mask = [&]() {   // a flavour that cannot evaluate the predicate itself: the mask after all
-    if (lazy) {
-      row_mask = lazy->mask();
-      lazy = nullptr;
-    }
-  };
-  // RightSemi / RightAnti emit probe columns only (joins/utils.rs:1628,1576): build_out_cols given by a C-ABI caller are ignored
-  // on every path — the fused kernel would otherwise gather build rows of unmatched (anti) probe rows
-  const std::vector<int> bout = (join_type == DFGPU_JOIN_RIGHT_SEMI || join_type == DFGPU_JOIN_RIGHT_ANTI) ? std::vector<int>{} : bout_in;
-  DFGPU_CHECK(pk.size() == jt.key_cols.size(), "probe key count differs from build key count");
-  DFGPU_CHECK(probe.device == jt.build.device, "the probe table lives on another device than the join table (move it with dfgpu_table_copy_to_device)");
-  if (jt.kind == KIND_RADIX) {
-    // the LDS radix join produces key-equal pairs; every join type is finished from them (row masks: the caller filters first)
-    if (row_mask || lazy) {
-      DFGPU_CHECK(mask_consumed != nullptr, "probe row mask without a fallback");
-      *mask_consumed = false;
-      return Table{};
-    }
-    if (join_type == DFGPU_JOIN_INNER && !jt.null_aware && pk.size() == 1) {
-      // INNER, fixed-width payload without NULLs: the emit walk writes the output columns itself (radix_join.hip, round 6)
-      for (int c : bout) DFGPU_CHECK(c >= 0 && c < (int)jt.build.cols.size(), "build output column out of range");
-      for (int c : pout) DFGPU_CHECK(c >= 0 && c < (int)probe.cols.size(), "probe output column out of range");
-      Table fused;
-      if (radix_join_inner_columns(*jt.radix, jt.build, jt.key_cols, probe, pk, bout, pout, fused)) {
-        std::lock_guard<std::mutex> lk(jt.mu);
-        jt.info.probe_rows += probe.nrows;
-        jt.info.output_rows += fused.nrows;
-        return fused;
-      }
-    }
-    return join_probe_with_filter(jt, probe, pk, join_type, bout, pout, nullptr);
+// ---- the probe: join_probe (the entry: arguments, visited bytes, counters), probe_core (plans the flavour once, then routes), one
+// function per flavour.  What the core is told about a probe it runs for another probe:
+struct ProbeHints {
+  bool keys_grouped = false;    // the probe over keys the grouped flavour grouped itself: clustered by construction
+  bool no_speculation = false;  // the counted probe that a speculation which met a row without a partner falls back to
+};
+// what is decided before the first flavour kernel; the device's answers revise it in plan_after_lookup, ask_all_hit, plan_after_counts
+struct ProbePlan {
+  bool probe_side_only, build_side_only, payload_nullable, fast_inner;
+  int64_t key_bytes, out_row_bytes;
+  bool fused_ok, want_single, use_fused, single_pass_pairs, rows_unused, big_table, unclustered, grouped_keys_only, first_match, one_match_path;
+  bool try_returned;       // the grouped lookup is to be asked
+  bool returned, returned_all_hit;   // (plan_after_lookup) it ran; every probe row found its key
+  bool listed;             // a guess until the counts pass has run (plan_after_counts)
+  bool pred_in_counts;     // the counts pass of the listed flavour evaluates the predicate itself; everything else reads a mask
+  int fused_mode;
+};
+// what the flavours share
+struct ProbeRun {
+  JoinTable& jt;
+  const Table& probe;
+  const std::vector<int>& pk;
+  int join_type;
+  const std::vector<int>&bout, &pout;
+  const uint64_t* row_mask;   // handed in, evaluated from `lazy` (need_mask), or the counts pass's output words
+  const LazyRowFilter* lazy;
+  bool* mask_consumed;
+  ProbeHints hints;
+  uint8_t* visited;   // the build side's visited bytes, for the join types that mark them
+  int64_t np, n_words;
+  int kind;  // what the probe kernels look the keys up in: the table, or (KIND_RETURNED) what a grouped lookup left per probe row
+  ProbeCtx ctx;
+  ProbePlan plan;
+  ReturnedProbe rp;   // what the grouped lookup left, when it ran
+  void set_row_mask(const uint64_t* m) { row_mask = ctx.row_mask = m; }
+  void need_mask() {   // a flavour that cannot evaluate the predicate itself: the mask after all
+    if (lazy) set_row_mask(lazy->mask());
+    lazy = nullptr;
   }
-  const int64_t np = probe.nrows;
-  const int64_t n_words = (np + 63) / 64;
-  int kind = jt.kind;  // what the probe kernels look the keys up in: the table, or (KIND_RETURNED) what a grouped lookup left per probe row
-  ProbeCtx ctx = make_ctx(jt, probe, pk, /*need_build_rows=*/false, /*want_tab=*/false);  // both decided below, once the probe flavour is known
-  auto need_tab = [&]() {
-    if (jt.kind == KIND_RANK) {
-      ensure_rank_tab(jt);
-      ctx.rank_tab = jt.rank_tab->as<ulonglong2>();
-    }
-  };
-  auto need_bits = [&]() {   // a pass that streams every probe key through the bitmap
-    if (jt.kind == KIND_RANK) {
-      ensure_rank_bits(jt);
-      ctx.rank_bits = jt.rank_bits->as<uint64_t>();
-    }
-  };
-  for (int c : bout) DFGPU_CHECK(c >= 0 && c < (int)jt.build.cols.size(), "build output column out of range");
-  for (int c : pout) DFGPU_CHECK(c >= 0 && c < (int)probe.cols.size(), "probe output column out of range");
-  uint8_t* visited = nullptr;
-  if (needs_visited(join_type)) {
-    {
-      std::lock_guard<std::mutex> lk(jt.mu);
-      if (!jt.visited) {
-        jt.visited = make_zero_buf((size_t)jt.build.nrows + 64);
-        DFGPU_HIP(hipStreamSynchronize(rt().stream));  // zeroed before any other thread's stream marks rows in it
-      }
-    }
-    visited = jt.visited->as<uint8_t>();
+  void need_tab() {
+    if (jt.kind != KIND_RANK) return;
+    ensure_rank_tab(jt);
+    ctx.rank_tab = jt.rank_tab->as<ulonglong2>();
   }
-  {
-    std::lock_guard<std::mutex> lk(jt.mu);
-    jt.info.probe_rows += np;
-  }
-  int64_t key_bytes = 0;
-  for (int i = 0; i < ctx.pkeys.n; i++) key_bytes += np * ctx.pkeys.c[i].width;
-  Table out;
-
-  const bool probe_side_only = join_type == DFGPU_JOIN_RIGHT_SEMI || join_type == DFGPU_JOIN_RIGHT_ANTI;
-  const bool build_side_only = join_type == DFGPU_JOIN_LEFT_SEMI || join_type == DFGPU_JOIN_LEFT_ANTI || join_type == DFGPU_JOIN_LEFT_MARK;
-  bool payload_nullable = false;
+};
+static Table probe_core(JoinTable& jt, const Table& probe, const std::vector<int>& pk, int join_type, const std::vector<int>& bout, const std::vector<int>& pout,
+                        const uint64_t* row_mask, bool* mask_consumed, const LazyRowFilter* lazy, ProbeHints hints, uint8_t* visited);
+static ProbePlan plan_probe(const ProbeRun& p) {
+  const JoinTable& jt = p.jt;
+  const Table& probe = p.probe;
+  const std::vector<int>&pk = p.pk, &bout = p.bout, &pout = p.pout;
+  const int64_t np = p.np;
+  const int join_type = p.join_type;
+  const bool masked = p.row_mask || p.lazy;
+  ProbePlan pl{};
+  for (int i = 0; i < p.ctx.pkeys.n; i++) pl.key_bytes += np * p.ctx.pkeys.c[i].width;
+  pl.probe_side_only = join_type == DFGPU_JOIN_RIGHT_SEMI || join_type == DFGPU_JOIN_RIGHT_ANTI;
+  pl.build_side_only = join_type == DFGPU_JOIN_LEFT_SEMI || join_type == DFGPU_JOIN_LEFT_ANTI || join_type == DFGPU_JOIN_LEFT_MARK;
   // (a Utf8 payload column takes the same route as a nullable one: pairs, then take — strings.hip gather_strings)
-  for (int c : bout) payload_nullable |= jt.build.cols[c].has_nulls() || jt.build.cols[c].field.type == DFGPU_UTF8;
-  for (int c : pout) payload_nullable |= probe.cols[c].has_nulls() || probe.cols[c].field.type == DFGPU_UTF8;
-  const bool fast_inner = join_type == DFGPU_JOIN_INNER && jt.keys_unique && !payload_nullable &&
-                          (int)(bout.size() + pout.size()) <= MAX_JOIN_COLS;
-
-  // single-pass flavour: output columns are allocated for the upper bound (np rows) because the
-  // row count is only known when the kernel ends; HBM is sized for that (288 GB)
-  int64_t out_row_bytes = 0;
-  if (!payload_nullable) {
-    for (int c : bout) out_row_bytes += type_width(jt.build.cols[c].field.type);
-    for (int c : pout) out_row_bytes += type_width(probe.cols[c].field.type);
+  for (int c : bout) pl.payload_nullable |= jt.build.cols[c].has_nulls() || jt.build.cols[c].field.type == DFGPU_UTF8;
+  for (int c : pout) pl.payload_nullable |= probe.cols[c].has_nulls() || probe.cols[c].field.type == DFGPU_UTF8;
+  pl.fast_inner = join_type == DFGPU_JOIN_INNER && jt.keys_unique && !pl.payload_nullable && (int)(bout.size() + pout.size()) <= MAX_JOIN_COLS;
+  if (!pl.payload_nullable) {
+    for (int c : bout) pl.out_row_bytes += type_width(jt.build.cols[c].field.type);
+    for (int c : pout) pl.out_row_bytes += type_width(probe.cols[c].field.type);
   }
-  const bool fused_ok = np < (1ll << 40) && !payload_nullable && (int)(bout.size() + pout.size()) <= MAX_JOIN_COLS &&
-                        bout.size() + pout.size() > 0 && (fast_inner || probe_side_only);
+  pl.fused_ok = np < (1ll << 40) && !pl.payload_nullable && (int)(bout.size() + pout.size()) <= MAX_JOIN_COLS && bout.size() + pout.size() > 0 &&
+                (pl.fast_inner || pl.probe_side_only);
   // probe_mode: 0 / 1 = output in probe order like the reference (exec.rs:3349), exact allocation: the PLACED flavour (tile
   // counts -> scan -> the fused kernel with known tile offsets) when it applies, else lookup -> scan -> materialise;
   // 2 = single pass ordered by decoupled look-back, 3 = single pass unordered (errors when not applicable);
   // 4 = a planner's hint "no ancestor needs the probe order": single pass unordered when applicable, the general path otherwise
-  const bool want_single = jt.probe_mode == 2 || jt.probe_mode == 3 || jt.probe_mode == 4;
-  const bool use_fused = fused_ok && np > 0;
+  pl.want_single = jt.probe_mode == 2 || jt.probe_mode == 3 || jt.probe_mode == 4;
+  pl.use_fused = pl.fused_ok && np > 0;
+  // LeftSemi/LeftAnti/LeftMark must mark EVERY matching build row: first-match suffices only for unique keys
+  pl.first_match = !pl.use_fused && np > 0 && (pl.probe_side_only || (pl.build_side_only && jt.keys_unique) || pl.fast_inner);
   // the general M:N path in one pass (k_probe_pairs_single): flat tables under the planner's hint that nobody observes the order
-  const bool single_pass_pairs = !use_fused && join_type == DFGPU_JOIN_INNER && jt.probe_mode == 4 && (jt.kind == KIND_FLAT || jt.kind == KIND_FLAT16) &&
-                                 !row_mask && !lazy && np >= (1 << 16) && np < 0xFFFFFFFFll &&
-                                 true;
+  pl.single_pass_pairs = !pl.use_fused && join_type == DFGPU_JOIN_INNER && jt.probe_mode == 4 && (jt.kind == KIND_FLAT || jt.kind == KIND_FLAT16) && !masked &&
+                         np >= (1 << 16) && np < 0xFFFFFFFFll;
   // A probe whose output holds no build column and that marks no build row only asks whether the key is THERE: over a rank map of
   // keys in no particular order it needs the bitmap alone, not the rank -> row permutation (which is built by the first probe
   // that does need rows)
-  const bool rows_unused = bout.empty() && !needs_visited(join_type) && (use_fused || probe_side_only);
+  pl.rows_unused = bout.empty() && !needs_visited(join_type) && (pl.use_fused || pl.probe_side_only);
   // what counts as "beyond the caches": 4 x the L2 of an XCD (16 MiB on MI355X), Policy::beyond_cache_bytes
   const int64_t big_bytes = option_int("join.beyond_cache_bytes", (int64_t)policy().beyond_cache_bytes());
-  const bool big_table = (jt.kind == KIND_RANK || jt.kind == KIND_ARRAY) && (int64_t)(jt.kind == KIND_RANK ? (jt.am_size >> 6) * 16 : jt.am_size * 4) > big_bytes;
-  static thread_local bool in_grouped_probe = false;  // the probe over keys this function grouped itself: clustered by construction
+  pl.big_table = (jt.kind == KIND_RANK || jt.kind == KIND_ARRAY) && (int64_t)(jt.kind == KIND_RANK ? (jt.am_size >> 6) * 16 : jt.am_size * 4) > big_bytes;
   // from how many probe rows grouping them first is considered: the extra move has to repay itself (Policy::rows_worth_a_pass)
   const int64_t grouped_min_rows = option_int("join.grouped_min_rows", policy().rows_worth_a_pass());
-  const bool unclustered = fused_ok && big_table && np > grouped_min_rows && pk.size() == 1 && !in_grouped_probe &&
-                           !probe_keys_clustered(probe.cols[(size_t)pk[0]], np,
-                                                 option_int("join.near_window", 0) ? (uint64_t)option_int("join.near_window", 0)   // (test hook)
-                                                 : jt.kind == KIND_RANK ? ((uint64_t)512 << 10) / 16 * 64 : ((uint64_t)512 << 10) / 4);
+  pl.unclustered = pl.fused_ok && pl.big_table && np > grouped_min_rows && pk.size() == 1 && !p.hints.keys_grouped &&
+                   !probe_keys_clustered(probe.cols[(size_t)pk[0]], np,
+                                         option_int("join.near_window", 0) ? (uint64_t)option_int("join.near_window", 0)   // (test hook)
+                                         : jt.kind == KIND_RANK ? ((uint64_t)512 << 10) / 16 * 64 : ((uint64_t)512 << 10) / 4);
   const bool group_env = option_on("join.grouped_probe", true);  // (A/B switch)
-  // the key-only probe whose order nobody observes: its keys are grouped and probed in group order (below)
-  const bool grouped_keys_only = unclustered && group_env && jt.probe_mode == 4 && rows_unused && !row_mask && !lazy && pout.size() == 1 && pout[0] == pk[0] &&
-                                 ctx.pkeys.c[0].width == 8 && !probe.cols[(size_t)pk[0]].validity;
+  // the key-only probe whose order nobody observes: its keys are grouped and probed in group order (probe_grouped_keys)
+  pl.grouped_keys_only = pl.unclustered && group_env && jt.probe_mode == 4 && pl.rows_unused && !masked && pout.size() == 1 && pout[0] == pk[0] &&
+                         p.ctx.pkeys.c[0].width == 8 && !probe.cols[(size_t)pk[0]].validity;
   // every other unclustered probe of a big rank map: the keys travel to the table group by group and what they found comes back
   // to the probe rows (k_gp_lookup above); the build rows are read at rank positions, so no rank -> row permutation is needed
-  const bool returned_env = true;
-  bool returned = use_fused && unclustered && group_env && returned_env && !grouped_keys_only && jt.kind == KIND_RANK && jt.probe_mode != 2 &&
-                  is_integer_like(probe.cols[(size_t)pk[0]].field.type);
-  if (trace_on("join"))   // one line per probe on stderr: what decided the probe flavour
-    fprintf(stderr, "[dfgpu join_probe] np=%lld kind=%d probe_mode=%d fused_ok=%d big_table=%d unclustered=%d grouped_keys_only=%d returned=%d rows_unused=%d row_mask=%d\n",
-            (long long)np, jt.kind, jt.probe_mode, (int)fused_ok, (int)big_table, (int)unclustered, (int)grouped_keys_only, (int)returned, (int)rows_unused, row_mask != nullptr);
-  ReturnedProbe rp;
-  if (returned) need_mask();
-  if (returned) returned = grouped_probe_lookup(jt, probe, pk[0], bout, row_mask, rp);
-  if (returned) {
-    kind = KIND_RETURNED;
-    ctx.ret_dest = rp.dest->as<uint32_t>();
-    ctx.ret_rec = rp.rec->as<uint8_t>();
-    ctx.ret_R = rp.R;
-  }
-  if (!returned && !rows_unused && jt.kind == KIND_RANK && jt.rank_needs_perm) {
-    ensure_rank_perm(jt);
-    ctx.rank_perm = jt.rank_perm->as<uint32_t>();
-    ctx.rank_tab = jt.rank_tab->as<ulonglong2>();
-  }
-  DFGPU_CHECK(!((jt.probe_mode == 2 || jt.probe_mode == 3) && !fused_ok),
-              "single-pass probe requested but not applicable (needs <=1 match per probe row and non-nullable payload)");
-  int fused_mode = !want_single ? FUSED_PLACED : jt.probe_mode == 2 ? FUSED_LOOKBACK : FUSED_UNORDERED;
+  pl.try_returned = pl.use_fused && pl.unclustered && group_env && !pl.grouped_keys_only && jt.kind == KIND_RANK && jt.probe_mode != 2 &&
+                    is_integer_like(probe.cols[(size_t)pk[0]].field.type);
+  pl.fused_mode = !pl.want_single ? FUSED_PLACED : jt.probe_mode == 2 ? FUSED_LOOKBACK : FUSED_UNORDERED;
   // Few output rows expected — a FilterExec fused below the probe side, or a build side that covers little of its key range
   // (the hit rate of foreign keys drawn from that range): counts + hit words, then k_join_emit_listed.  The counts pass
   // knows the answer before the second kernel is chosen, so a wrong guess costs the counts pass, not the result; the
   // output is in probe order, which every probe_mode accepts.
-  bool listed = fused_ok && fused_mode != FUSED_LOOKBACK && (kind == KIND_RANK || kind == KIND_ARRAY) &&
-                (row_mask != nullptr || lazy != nullptr || (double)jt.build.nrows < 0.15 * (double)jt.am_size);
-  // what the grouped lookup found decides the placement: every probe row matched — row i of the output is probe row i, no counts
-  // pass; else the cursor when nobody observes the order, else counts + placed
-  const bool returned_all_hit = returned && rp.hits == np && !row_mask && join_type != DFGPU_JOIN_RIGHT_ANTI;
-  if (returned && !returned_all_hit && fused_mode != FUSED_LOOKBACK) fused_mode = want_single ? FUSED_UNORDERED : FUSED_PLACED;
-  if (returned_all_hit) fused_mode = FUSED_PLACED;
-  if (listed) fused_mode = FUSED_PLACED;
+  pl.listed = pl.fused_ok && pl.fused_mode != FUSED_LOOKBACK && (jt.kind == KIND_RANK || jt.kind == KIND_ARRAY) &&
+              (masked || (double)jt.build.nrows < 0.15 * (double)jt.am_size);
+  if (pl.listed) pl.fused_mode = FUSED_PLACED;
   // The unordered flavour claims every 2048-row tile's output range with one returning atomicAdd on ONE cursor, and a contended
   // agent-scope atomic retires one claim per ~12 ns (scripts/microbench/tile_atomics.hip): 3.5 ms for an SF100 probe's 293 K
   // tiles.  A tile of narrow rows streams in less than that — a key-only join moves 16 B per probe row: 5 ns per tile — so the
@@ -3189,55 +3141,11 @@ static Table join_probe(JoinTable& jt, const Table& probe, const std::vector<int
   //  * the probe reads nothing but its key and nobody observes its order (SELECT l.k ... JOIN, the reference's hj.rs shapes;
   //    semi / anti joins on the key alone): ONE stable radix pass groups the probe keys by the top bits of their range
   //    (sort.hip's pass, 64 groups: a group's slice of the table is ~1/64 of it and sits in L2), then the ordinary probe runs
-  //    over the grouped keys — lookups hit lines their neighbours fetched;
+  //    over the grouped keys — lookups hit lines their neighbours fetched (grouped_keys_only);
   //  * otherwise the single-pass probe: one lookup per row.
-  if (grouped_keys_only) {
-    const Column& kc = probe.cols[(size_t)pk[0]];
-    BufPtr keys = kc.data;
-    if (kc.data_offset != 0) {  // a slice of a larger buffer: the pass wants its own
-      keys = make_buf((size_t)np * 8);
-      DFGPU_HIP(hipMemcpyAsync(keys->ptr, kc.ptr(), (size_t)np * 8, hipMemcpyDeviceToDevice, r.stream));
-    }
-    int64_t n_grouped = np;
-    if (jt.kind == KIND_RANK && join_type != DFGPU_JOIN_RIGHT_ANTI) {
-      // round 4: grouped by their position in the table's key range (grouped.hip: one pass, 2^9 groups or so); keys outside the
-      // range — they match nothing, and an Inner / RightSemi probe emits nothing for them — drop out here
-      const KeyCol key{kc.ptr(), nullptr, kc.field.type, 8};
-      const int nbits = gp_bits_for(jt, 0);
-      GroupedRows gr = group_rows_by_key(key, np, gp_spec_for(jt, nbits), nbits, nullptr, true, false, {}, {}, "join_probe_group_keys");
-      keys = gr.keys;
-      n_grouped = gr.rows;
-    } else {
-    int range_bits = 0;
-    while (range_bits < 64 && (jt.am_size >> range_bits)) range_bits++;
-    // groups = keys sharing bits [range_bits - 6, range_bits) of their value: at most two stretches of the key range each
-    radix_group_keys(keys, np, std::max(0, range_bits - 6), 6);
-    }
-    Table grouped;
-    grouped.nrows = n_grouped;
-    grouped.device = probe.device;
-    Column gk = kc;
-    gk.data = keys;
-    gk.data_offset = 0;
-    gk.length = n_grouped;
-    gk.stats.reset();
-    grouped.cols.push_back(std::move(gk));
-    in_grouped_probe = true;
-    Table res;
-    try {
-      res = join_probe(jt, grouped, {0}, join_type, bout_in, {0}, nullptr, nullptr);
-    } catch (...) {
-      in_grouped_probe = false;
-      throw;
-    }
-    in_grouped_probe = false;
-    std::lock_guard<std::mutex> lk(jt.mu);
-    jt.info.probe_rows -= n_grouped;  // counted by the inner call as well
-    return res;
-  }
-  // (the probe over keys grouped above: its lookups hit L2 but are still one line request per row — one pass, not two)
-  if (fused_ok && fused_mode == FUSED_UNORDERED && np > (1 << 22) && !unclustered && !in_grouped_probe && !returned) {
-    int64_t row_bytes = key_bytes / std::max<int64_t>(np, 1) + out_row_bytes;
+  // (the probe over keys grouped that way: its lookups hit L2 but are still one line request per row — one pass, not two)
+  if (pl.fused_ok && pl.fused_mode == FUSED_UNORDERED && np > (1 << 22) && !pl.unclustered && !p.hints.keys_grouped) {
+    int64_t row_bytes = pl.key_bytes / std::max<int64_t>(np, 1) + pl.out_row_bytes;
     for (int c : pout) {
       bool is_key = false;
       for (int k : pk) is_key |= k == c;
@@ -3245,424 +3153,516 @@ static Table join_probe(JoinTable& jt, const Table& probe, const std::vector<int
     }
     // tile bytes / (6000 B per ns) below one claim's 12 ns: < 35 B per probe row.  (At two claims' worth the counts pass cost more
     // than the cursor did: a 40-byte semi-join probe of 72 M rows went from 0.35 to 0.8 ms.)
-    if (row_bytes * (FUSED_W * BLOCK) < 12 * 6000) fused_mode = FUSED_PLACED;
+    if (row_bytes * (FUSED_W * BLOCK) < 12 * 6000) pl.fused_mode = FUSED_PLACED;
   }
   // A probe-side row mask is applied in place by the at-most-one-match probes (fused, or lookup -> scan ->
   // materialise); the general pairs path needs the caller to filter first.
-  const bool one_match_path = np > 0 && (probe_side_only || fast_inner);
-  const bool use_fused_now = use_fused;
-  // the counts pass of the listed flavour evaluates the predicate itself; everything else reads a mask
-  const bool pred_in_counts = lazy != nullptr && use_fused && listed && fused_mode == FUSED_PLACED && !returned && (kind == KIND_RANK || kind == KIND_ARRAY);
-  if (!pred_in_counts) need_mask();
-  if (row_mask || pred_in_counts) {
+  pl.one_match_path = np > 0 && (pl.probe_side_only || pl.fast_inner);
+  return pl;
+}
+// what the grouped lookup found decides the placement: every probe row matched — row i of the output is probe row i, no counts
+// pass; else the cursor when nobody observes the order, else counts + placed.  A lookup that declined leaves the plan as it was.
+static void plan_after_lookup(ProbePlan& pl, const ProbeRun& p, bool ran) {
+  pl.returned = ran;
+  if (!ran) return;
+  pl.returned_all_hit = p.rp.hits == p.np && !p.row_mask && p.join_type != DFGPU_JOIN_RIGHT_ANTI;
+  pl.listed = false;   // (the listed emit reads the table's bitmap, not the records that came back)
+  pl.fused_mode = pl.returned_all_hit || !pl.want_single ? FUSED_PLACED : FUSED_UNORDERED;
+}
+// n_alloc rows come out, the counts pass says: denser than guessed — the placed kernel streams better than it lists
+static void plan_after_counts(ProbePlan& pl, int64_t n_alloc, int64_t np) { pl.listed = pl.listed && n_alloc * 4 <= np; }
+// appends `cols` of one side to the output table (`rows` rows each) and to the kernel's copy list; returns the bytes of one row of them
+static int64_t add_copy_cols(const Table& side, const std::vector<int>& cols, int64_t rows, Table& out, JoinCopyCols& jc) {
+  int64_t row_bytes = 0;
+  for (int c : cols) {
+    const Column& sc = side.cols[c];
+    out.cols.push_back(alloc_like(sc, rows));
+    jc.src[jc.n] = sc.ptr();
+    jc.dst[jc.n] = out.cols.back().data->ptr;
+    jc.width[jc.n] = type_width(sc.field.type);
+    row_bytes += jc.width[jc.n++];
+  }
+  return row_bytes;
+}
+static Table probe_radix(JoinTable& jt, const Table& probe, const std::vector<int>& pk, int join_type, const std::vector<int>& bout, const std::vector<int>& pout,
+                         bool masked, bool* mask_consumed) {
+  // the LDS radix join produces key-equal pairs; every join type is finished from them (row masks: the caller filters first)
+  if (masked) {
     DFGPU_CHECK(mask_consumed != nullptr, "probe row mask without a fallback");
-    *mask_consumed = use_fused || one_match_path;
+    *mask_consumed = false;
+    return Table{};
+  }
+  if (join_type == DFGPU_JOIN_INNER && !jt.null_aware && pk.size() == 1) {
+    // INNER, fixed-width payload without NULLs: the emit walk writes the output columns itself (radix_join.hip, round 6)
+    Table fused;
+    if (radix_join_inner_columns(*jt.radix, jt.build, jt.key_cols, probe, pk, bout, pout, fused)) {
+      std::lock_guard<std::mutex> lk(jt.mu);
+      jt.info.probe_rows += probe.nrows;
+      jt.info.output_rows += fused.nrows;
+      return fused;
+    }
+  }
+  return join_probe_with_filter(jt, probe, pk, join_type, bout, pout, nullptr);
+}
+// the key-only probe of unclustered keys (plan_probe): group the keys, then the ordinary probe over them
+static Table probe_grouped_keys(ProbeRun& p) {
+  JoinTable& jt = p.jt;
+  const int64_t np = p.np;
+  const Column& kc = p.probe.cols[(size_t)p.pk[0]];
+  BufPtr keys = kc.data;
+  if (kc.data_offset != 0) {  // a slice of a larger buffer: the pass wants its own
+    keys = make_buf((size_t)np * 8);
+    DFGPU_HIP(hipMemcpyAsync(keys->ptr, kc.ptr(), (size_t)np * 8, hipMemcpyDeviceToDevice, rt().stream));
+  }
+  int64_t n_grouped = np;
+  if (jt.kind == KIND_RANK && p.join_type != DFGPU_JOIN_RIGHT_ANTI) {
+    // round 4: grouped by their position in the table's key range (grouped.hip: one pass, 2^9 groups or so); keys outside the
+    // range — they match nothing, and an Inner / RightSemi probe emits nothing for them — drop out here
+    const KeyCol key{kc.ptr(), nullptr, kc.field.type, 8};
+    const int nbits = gp_bits_for(jt, 0);
+    GroupedRows gr = group_rows_by_key(key, np, gp_spec_for(jt, nbits), nbits, nullptr, true, false, {}, {}, "join_probe_group_keys");
+    keys = gr.keys;
+    n_grouped = gr.rows;
+  } else {
+    int range_bits = 0;
+    while (range_bits < 64 && (jt.am_size >> range_bits)) range_bits++;
+    // groups = keys sharing bits [range_bits - 6, range_bits) of their value: at most two stretches of the key range each
+    radix_group_keys(keys, np, std::max(0, range_bits - 6), 6);
+  }
+  Table grouped;
+  grouped.nrows = n_grouped;
+  grouped.device = p.probe.device;
+  Column gk = kc;
+  gk.data = keys;
+  gk.data_offset = 0;
+  gk.length = n_grouped;
+  gk.stats.reset();
+  grouped.cols.push_back(std::move(gk));
+  const std::vector<int> key_col{0};
+  return probe_core(jt, grouped, key_col, p.join_type, p.bout, key_col, nullptr, nullptr, nullptr, ProbeHints{true, p.hints.no_speculation}, nullptr);
+}
+// ---- speculation for the probe-order output: a foreign-key probe (every row finds its key) needs no counts pass — row i of
+// the output IS probe row i.  64 K sampled rows that all hit make it worth trying; the kernel verifies every row and the
+// host starts over with the counts when one disagrees (the reference's order, exec.rs:3349, at the unordered flavour's cost)
+struct Speculation {
+  bool shared = false, placed = false;   // every row hits: the shared flavour, else the placed flavour without its counts pass
+  DevBuf* hit_hint = nullptr;   // where the sample's answer is remembered (all_hit_tag), when it was asked
+  uint64_t hit_tag = 0;
+};
+static Speculation ask_all_hit(ProbeRun& p, int invert) {
+  const ProbePlan& pl = p.plan;
+  const int kind = p.kind;
+  Speculation s;
+  bool all_hit = false;
+  const bool spec_kind = kind == KIND_RANK || kind == KIND_ARRAY || kind == KIND_FLAT || kind == KIND_FLAT16;
+  // from how many probe rows the sample (a kernel and a blocking read-back) is worth its answer
+  const bool may_sample = !p.row_mask && !p.lazy && !invert && !p.hints.no_speculation && spec_kind && p.np >= option_int("join.share_probe_min_rows", 1 << 22);
+  // ---- the shared flavour (k_join_probe_shared): when every row hits and the output is in probe order — required by probe_mode
+  // 0 / 1, one admissible order for 3 / 4 — the output's probe-side columns ARE the probe table's columns (immutable, reference-
+  // counted buffers: second owners, as dfgpu_table_select hands out) and only the build-side columns are written.  `listed` resting
+  // on the key-density guess alone does not keep an all-hit probe away: the sample is asked first, and a sample that finds a miss
+  // leaves `listed` and everything below as it was.
+  const bool share_wanted = option_on("join.share_probe", true) && p.jt.probe_mode != 2 && !pl.returned && (pl.fast_inner || p.join_type == DFGPU_JOIN_RIGHT_SEMI);
+  if (pl.returned_all_hit && !p.hints.no_speculation) {
+    all_hit = true;   // (not a guess here: the grouped lookup counted its hits; the kernel's per-tile check stays as the safety net)
+  } else if (may_sample && (share_wanted || (pl.fused_mode == FUSED_PLACED && !pl.listed))) {
+    // asked before of these key buffers?  (a kernel and a blocking read-back, 0.04 ms, on every unmasked fused probe otherwise)
+    s.hit_hint = p.probe.cols[(size_t)p.pk[0]].data.get();
+    s.hit_tag = all_hit_tag(p.jt, p.probe, p.pk, kind);
+    const uint64_t h = s.hit_hint->all_hit_hint.load(std::memory_order_relaxed);
+    if ((h & ~1ull) == s.hit_tag) {
+      all_hit = (h & 1ull) != 0;
+    } else {
+      constexpr int S = 1024;  // sampled words
+      BufPtr miss = make_zero_buf(4);
+      with_kind_and_key(kind, p.ctx.pkeys.c[0].type, [&](auto kd, auto kt) {
+        k_sample_all_hit<decltype(kd)::value, decltype(kt)::value><<<S * WAVE / BLOCK, BLOCK, 0, rt().stream>>>(p.ctx, p.np, std::max<int64_t>(1, p.n_words / S), S, miss->as<int>());
+      });
+      DFGPU_HIP(hipGetLastError());
+      int m = 0;
+      d2h(&m, miss->ptr, 4);
+      all_hit = m == 0;
+      s.hit_hint->all_hit_hint.store(s.hit_tag | (all_hit ? 1ull : 0ull), std::memory_order_relaxed);
+    }
+  }
+  s.shared = all_hit && share_wanted && !pl.returned_all_hit;
+  s.placed = all_hit && !s.shared && pl.fused_mode == FUSED_PLACED && !pl.listed;   // (asked for the shared flavour only: nothing else to speculate on)
+  return s;
+}
+// the same probe again, counted: what a speculation that met a row without a partner falls back to
+static Table probe_again_counted(ProbeRun& p, const Speculation& s, LateRecord& launch, Table& half_made) {
+  if (s.hit_hint) s.hit_hint->all_hit_hint.store(s.hit_tag, std::memory_order_relaxed);   // (the sample was wrong about these rows: not asked again)
+  launch.record("join_probe_speculation_missed", 0);
+  half_made = Table{};   // (the half-made output goes back to the pool first)
+  return probe_core(p.jt, p.probe, p.pk, p.join_type, p.bout, p.pout, p.row_mask, p.mask_consumed, nullptr, ProbeHints{p.hints.keys_grouped, true}, p.visited);
+}
+static Table probe_shared(ProbeRun& p, const Speculation& spec) {
+  Runtime& r = rt();
+  const int64_t np = p.np, n_words = p.n_words;
+  p.need_tab();   // (a probe `listed` by the guess has not asked for the interleaved rank table yet)
+  Table out;
+  JoinCopyCols jc{};
+  jc.key_col = -1;
+  // what this launch moves: the keys once, the build payload once, the build-side output once
+  const int64_t bytes = p.plan.key_bytes + (p.jt.build.nrows + np) * add_copy_cols(p.jt.build, p.bout, np, out, jc);
+  jc.n_build = jc.n;
+  // where the kernel reports a miss: the thread's word of pinned host memory, zeroed here (the stream is idle with respect to
+  // it: every earlier probe of this thread waited for its kernel); else a device control word, with its fill and its copy
+  HostFlag* box = option_on("join.probe_host_flag", true) ? thread_host_flag() : nullptr;
+  BufPtr ctl = box ? nullptr : make_zero_buf(sizeof(FusedCtl));
+  unsigned* miss_flag = box ? box->dev : &ctl->as<FusedCtl>()->ticket;
+  if (box) *box->host = 0u;
+  LateRecord launch;
+  with_kind_and_key(p.kind, p.ctx.pkeys.c[0].type, [&](auto kd, auto kt) {
+    constexpr int K = decltype(kd)::value, T = decltype(kt)::value;
+    if constexpr (K == KIND_RANK || K == KIND_ARRAY || K == KIND_FLAT || K == KIND_FLAT16) {
+      const int64_t waves = (n_words + SHARED_W - 1) / SHARED_W;
+      const unsigned g = (unsigned)((waves + BLOCK / WAVE - 1) / (BLOCK / WAVE));
+      k_join_probe_shared<K, T, SHARED_W><<<g, BLOCK, 0, r.stream>>>(p.ctx, jc, np, miss_flag);
+    }
+  });
+  DFGPU_HIP(hipGetLastError());
+  launch.stop();
+  unsigned missed = 0;   // the one read-back: the output's row count is np without asking
+  if (box) {
+    DFGPU_HIP(hipStreamSynchronize(r.stream));
+    missed = *box->host;
+  } else {
+    d2h(&missed, miss_flag, 4);
+  }
+  if (missed) return probe_again_counted(p, spec, launch, out);
+  for (int c : p.pout) {   // second owners of the probe's buffers; the rows are the same rows, so the statistics stay
+    out.cols.push_back(p.probe.cols[c]);
+    out.cols.back().length = np;
+  }
+  launch.record(p.plan.want_single ? "join_probe_fused" : "join_probe_placed", bytes);
+  LateRecord::label("join_probe_shared_columns");   // (which path ran; moves nothing)
+  out.nrows = np;
+  return out;
+}
+// pass 1 of placed / listed: output rows per tile (reads the probe keys only), then the tiles' exclusive prefix; returns the row count
+static int64_t fused_counts_pass(ProbeRun& p, int64_t n_tiles, int invert, BufPtr& state, BufPtr& out_words) {
+  Runtime& r = rt();
+  ProbePlan& pl = p.plan;
+  const int64_t np = p.np;
+  BufPtr counts = make_buf((size_t)n_tiles * 4);
+  state = make_buf((size_t)(n_tiles + 1) * 8);
+  if (pl.listed) out_words = make_buf((size_t)p.n_words * 8);
+  if (p.kind == KIND_RANK) {   // a pass that streams every probe key through the bitmap
+    ensure_rank_bits(p.jt);
+    p.ctx.rank_bits = p.jt.rank_bits->as<uint64_t>();
+  }
+  {
+    ProfileScope ps("join_probe_tile_counts", pl.key_bytes + (pl.pred_in_counts ? np * p.lazy->pred_bytes_per_row : 0));
+    with_kind_and_key(p.kind, p.ctx.pkeys.c[0].type, [&](auto kd, auto kt) {
+      constexpr int K = decltype(kd)::value, T = decltype(kt)::value;
+      uint64_t* const words = out_words ? out_words->as<uint64_t>() : nullptr;
+      if constexpr (kind_is_direct<K>()) {
+        const bool nt = option_on("join.counts_nt", true);
+        if (pl.pred_in_counts) {
+          if (nt) k_join_tile_counts<K, T, FUSED_W, true, true><<<(unsigned)n_tiles, BLOCK, 0, r.stream>>>(p.ctx, np, invert, nullptr, counts->as<uint32_t>(), words, p.lazy->pred);
+          else k_join_tile_counts<K, T, FUSED_W, true><<<(unsigned)n_tiles, BLOCK, 0, r.stream>>>(p.ctx, np, invert, nullptr, counts->as<uint32_t>(), words, p.lazy->pred);
+          return;
+        }
+        if (nt) {
+          k_join_tile_counts<K, T, FUSED_W, false, true><<<(unsigned)n_tiles, BLOCK, 0, r.stream>>>(p.ctx, np, invert, p.row_mask, counts->as<uint32_t>(), words);
+          return;
+        }
+      }
+      k_join_tile_counts<K, T, FUSED_W><<<(unsigned)n_tiles, BLOCK, 0, r.stream>>>(p.ctx, np, invert, p.row_mask, counts->as<uint32_t>(), words);
+    });
+    DFGPU_HIP(hipGetLastError());
+  }
+  scan_u32(counts->as<uint32_t>(), n_tiles, state->as<uint64_t>());
+  const int64_t n_alloc = (int64_t)read_u64(state->as<uint64_t>() + n_tiles);
+  plan_after_counts(pl, n_alloc, np);
+  if (!pl.listed) p.need_tab();
+  // the placed kernel wants a row mask: the counts pass's output words ARE one — (hit & predicate) read as "rows that exist"
+  // selects exactly the rows that come out, for the inverted (anti) probe as well
+  if (pl.pred_in_counts && !pl.listed) p.set_row_mask(out_words->as<uint64_t>());
+  return n_alloc;
+}
+// the fused flavours: shared columns when every row hits, else [counts pass ->] placed / listed, or look-back / unordered in one pass
+static Table probe_fused(ProbeRun& p) {
+  Runtime& r = rt();
+  ProbePlan& pl = p.plan;
+  const int64_t np = p.np, n_words = p.n_words;
+  const int fused_mode = pl.fused_mode;
+  const int64_t tile_words = (int64_t)FUSED_W * (BLOCK / WAVE), n_tiles = (n_words + tile_words - 1) / tile_words;
+  const int invert = p.join_type == DFGPU_JOIN_RIGHT_ANTI;
+  BufPtr state = fused_mode == FUSED_LOOKBACK ? make_zero_buf((size_t)n_tiles * 8) : nullptr;
+  const Speculation spec = ask_all_hit(p, invert);
+  if (spec.shared) return probe_shared(p, spec);   // (it reports to the host directly and needs no control word)
+  // (every other flavour zeroes its control word here, ahead of its counts pass, as ever: the fill is then not what its kernel waits for)
+  BufPtr ctl = make_zero_buf(sizeof(FusedCtl));
+  BufPtr out_words;
+  const int64_t n_alloc = fused_mode == FUSED_PLACED && !spec.placed ? fused_counts_pass(p, n_tiles, invert, state, out_words) : np;
+  const bool listed = pl.listed;   // (no longer a guess)
+  Table out;
+  JoinCopyCols jc{};
+  jc.key_col = -1;
+  const int64_t build_row_bytes = add_copy_cols(p.jt.build, p.bout, n_alloc, out, jc);
+  jc.n_build = jc.n;
+  if (pl.returned)   // the columns' values came back inside the records
+    for (int i = 0; i < jc.n_build; i++) {
+      jc.src[i] = p.rp.rec->ptr;
+      jc.ret_mul[i] = p.rp.mul[(size_t)i];
+      jc.ret_add[i] = p.rp.add[(size_t)i];
+    }
+  const int64_t bytes_per_out = build_row_bytes + add_copy_cols(p.probe, p.pout, n_alloc, out, jc), bytes_build_once = p.jt.build.nrows * build_row_bytes;
+  int64_t bytes_in = pl.key_bytes;
+  for (size_t i = 0; i < p.pout.size(); i++) {
+    const int c = p.pout[i], at = jc.n_build + (int)i;
+    bool is_key = false;
+    for (int k : p.pk) is_key |= k == c;
+    if (!is_key) bytes_in += np * jc.width[at];  // a key column that is also payload is read once
+    if (is_key && (p.kind == KIND_ARRAY || p.kind == KIND_RANK) && p.pk.size() == 1 && jc.key_col < 0 && !p.probe.cols[c].validity) jc.key_col = at;
+  }
+  LateRecord launch;
+  int64_t n_out = n_alloc;
+  if (fused_mode != FUSED_PLACED || n_alloc > 0) {
+    // look-back: persistent workgroups pulling tickets; unordered / placed: one workgroup per tile
+    const unsigned g = fused_mode == FUSED_LOOKBACK ? (unsigned)std::min<int64_t>(n_tiles, (int64_t)r.num_cus * 8) : (unsigned)n_tiles;
+    uint64_t* st = state ? state->as<uint64_t>() : nullptr;
+    FusedCtl* const d_ctl = ctl->as<FusedCtl>();
+    auto launch_fused = [&](auto kern) { kern<<<g, BLOCK, 0, r.stream>>>(p.ctx, jc, np, invert, st, d_ctl, p.row_mask); };
+    with_kind_and_key(p.kind, p.ctx.pkeys.c[0].type, [&](auto kd, auto kt) {
+      constexpr int K = decltype(kd)::value, T = decltype(kt)::value;
+      constexpr bool KR = kind_is_direct<K>();  // the direct-address kinds hold the one integer key in registers
+      if constexpr (KR) {
+        if (listed) {
+          // (sparse: fewer than one row in `join.listed_sparse_den` comes out)
+          const int64_t den = option_int("join.listed_sparse_den", 32);   // (0: never)
+          if (den > 0 && n_alloc * den <= np) {
+            const int64_t groups = (n_words + EL_WORDS_SPARSE - 1) / EL_WORDS_SPARSE;
+            k_join_emit_listed<K, T, EL_WORDS_SPARSE><<<(unsigned)groups, BLOCK, 0, r.stream>>>(p.ctx, jc, np, out_words->as<uint64_t>(), st, (int)(EL_WORDS_SPARSE / tile_words));
+          } else {
+            const int64_t groups = (n_words + EL_WORDS - 1) / EL_WORDS;
+            k_join_emit_listed<K, T, EL_WORDS><<<(unsigned)groups, BLOCK, 0, r.stream>>>(p.ctx, jc, np, out_words->as<uint64_t>(), st, (int)(EL_WORDS / tile_words));
+          }
+          return;
+        }
+      }
+      if (fused_mode == FUSED_LOOKBACK) launch_fused(k_join_probe_fused<K, T, FUSED_W, FUSED_LOOKBACK, false>);
+      else if (fused_mode == FUSED_PLACED && KR && jc.key_col >= 0) launch_fused(k_join_probe_fused<K, T, FUSED_W, FUSED_PLACED, KR>);
+      else if (fused_mode == FUSED_PLACED) launch_fused(k_join_probe_fused<K, T, FUSED_W, FUSED_PLACED, false>);
+      else if (KR && jc.key_col >= 0) launch_fused(k_join_probe_fused<K, T, FUSED_W, FUSED_UNORDERED, KR>);
+      else launch_fused(k_join_probe_fused<K, T, FUSED_W, FUSED_UNORDERED, false>);
+    });
+    DFGPU_HIP(hipGetLastError());
+    launch.stop();
+    if (fused_mode != FUSED_PLACED) n_out = (int64_t)read_u64(reinterpret_cast<const uint64_t*>(&d_ctl->total));
+    if (spec.placed) {
+      unsigned missed = 0;
+      d2h(&missed, &d_ctl->ticket, 4);
+      if (missed) return probe_again_counted(p, spec, launch, out);   // some probe row has no partner after all
+    }
+  } else {
+    launch.stop();
+  }
+  // algorithmic bytes of this launch (SURVEY 8d config 3 ii): every referenced probe column once, the build payload
+  // columns once, the output written once (re-reads of build rows matched by several probe rows, table words, tile
+  // state are overhead); known only now that n_out is
+  launch.record(listed ? "join_probe_listed" : fused_mode == FUSED_PLACED ? "join_probe_placed" : "join_probe_fused",
+                bytes_in + (n_out > 0 ? bytes_build_once : 0) + n_out * bytes_per_out);
+  out.nrows = n_out;
+  for (Column& c : out.cols) c.length = n_out;
+  return out;
+}
+// ---- at most one match per probe row: lookup, then compaction (probe side only), marks alone (build side only) or scan -> materialise
+static Table probe_first_match(ProbeRun& p) {
+  Runtime& r = rt();
+  const ProbePlan& pl = p.plan;
+  const int64_t np = p.np, n_words = p.n_words;
+  Table out;
+  BufPtr mask = make_buf(bitmap_bytes(np));
+  BufPtr first = pl.fast_inner ? make_buf((size_t)np * 4) : nullptr;
+  {
+    ProfileScope ps("join_probe_lookup", pl.key_bytes);  // algorithmic: the probe keys (table reads / match ids are overhead)
+    const int g = grid_for(n_words, (BLOCK / WAVE) * PROBE_UNROLL), invert = p.join_type == DFGPU_JOIN_RIGHT_ANTI;
+    with_kind_and_key(p.jt.kind, p.ctx.pkeys.c[0].type, [&](auto kd, auto kt) {
+      k_probe_first<decltype(kd)::value, decltype(kt)::value><<<g, BLOCK, 0, r.stream>>>(p.ctx, np, invert, first ? first->as<uint32_t>() : nullptr,
+                                                                                         mask->as<uint64_t>(), p.visited);
+    });
+    DFGPU_HIP(hipGetLastError());
+  }
+  if (pl.probe_side_only) return compact_table(p.probe, p.pout, mask->as<uint64_t>(), nullptr);
+  if (pl.build_side_only) {   // no rows here: emitted by dfgpu_join_emit_unmatched
+    for (int c : p.bout) out.cols.push_back(alloc_like(p.jt.build.cols[c], 0));
+    return out;
+  }
+  BufPtr prefix = make_buf((size_t)(n_words + 1) * 8);
+  scan_mask_popcounts(mask->as<uint64_t>(), nullptr, np, prefix->as<uint64_t>());
+  const int64_t n_out = (int64_t)read_u64(prefix->as<uint64_t>() + n_words);
+  out.nrows = n_out;
+  JoinCopyCols jc{};
+  // algorithmic bytes: probe payload read once, build payload read per output row, output
+  // written once (mask / match-id traffic is overhead and not counted)
+  int64_t bytes = 2 * n_out * add_copy_cols(p.jt.build, p.bout, n_out, out, jc);
+  jc.n_build = jc.n;
+  bytes += (np + n_out) * add_copy_cols(p.probe, p.pout, n_out, out, jc);
+  if (n_out > 0 && jc.n > 0) {
+    ProfileScope ps("join_probe_materialize", bytes);
+    k_join_materialize<<<grid_for(n_words, (BLOCK / WAVE) * PROBE_UNROLL), BLOCK, 0, r.stream>>>(jc, mask->as<uint64_t>(), prefix->as<uint64_t>(),
+                                                                                                  first->as<uint32_t>(), np);
+    DFGPU_HIP(hipGetLastError());
+  }
+  return out;
+}
+// ---- general M:N path in one pass (flat tables, INNER, order unobserved): sample -> pairs at a cursor -> gathers
+static Table probe_pairs_single(ProbeRun& p) {
+  Runtime& r = rt();
+  const JoinTable& jt = p.jt;
+  const int64_t np = p.np, n_words = p.n_words;
+  constexpr int64_t SAMPLE = 1 << 16;
+  const int64_t every = std::max<int64_t>(1, np / SAMPLE), n_sample = (np + every - 1) / every;
+  BufPtr ctl = make_zero_buf(16);
+  with_kind(jt.kind, [&](auto kt) {
+    constexpr int K = decltype(kt)::value;
+    if constexpr (kind_is_flat<K>()) k_probe_pairs_sample<K><<<grid_for(n_sample, BLOCK), BLOCK, 0, r.stream>>>(p.ctx, np, every, n_sample, ctl->as<unsigned long long>());
+  });
+  unsigned long long seen = 0;
+  d2h(&seen, ctl->ptr, 8);
+  // (the sample's pairs scaled to the probe side, a quarter more and a constant: an underestimate costs one more pass at the exact size)
+  unsigned long long capacity = (unsigned long long)((double)seen * (double)np / (double)n_sample * 1.25) + (1ull << 16);
+  BufPtr ob, op;
+  unsigned long long total = 0;
+  for (int attempt = 0; attempt < 2; attempt++) {
+    ob = make_buf((size_t)capacity * 8);
+    op = make_buf((size_t)capacity * 8);
+    DFGPU_HIP(hipMemsetAsync(ctl->ptr, 0, 16, r.stream));
+    {
+      ProfileScope ps("join_probe_pairs_single", p.plan.key_bytes + (int64_t)capacity * 16);
+      const int g = (int)std::min<int64_t>((n_words + PROBE_UNROLL * (BLOCK / WAVE) - 1) / (PROBE_UNROLL * (BLOCK / WAVE)), (int64_t)r.num_cus * 16);
+      with_kind(jt.kind, [&](auto kt) {
+        constexpr int K = decltype(kt)::value;
+        if constexpr (kind_is_flat<K>()) k_probe_pairs_single<K><<<g, BLOCK, 0, r.stream>>>(p.ctx, np, ctl->as<unsigned long long>(), capacity, ob->as<int64_t>(), op->as<int64_t>());
+      });
+      DFGPU_HIP(hipGetLastError());
+    }
+    d2h(&total, ctl->ptr, 8);
+    if (total <= capacity) break;
+    DFGPU_CHECK(attempt == 0, "join: the single-pass probe overflowed a buffer of its exact size");
+    capacity = total;   // (the cursor counted every pair: the second try fits)
+  }
+  Table out;
+  out.nrows = (int64_t)total;
+  for (Column& c : gather_columns(jt.build, p.bout, ob->as<int64_t>(), out.nrows, false)) out.cols.push_back(std::move(c));
+  for (Column& c : gather_columns(p.probe, p.pout, op->as<int64_t>(), out.nrows, false)) out.cols.push_back(std::move(c));
+  return out;
+}
+// ---- general M:N path: counts -> scan -> pairs -> gathers
+static Table probe_pairs(ProbeRun& p) {
+  Runtime& r = rt();
+  const int join_type = p.join_type;
+  const int64_t np = p.np, n_words = p.n_words, key_bytes = p.plan.key_bytes;
+  BufPtr row_counts = make_buf((size_t)(np ? np : 1) * 4);
+  BufPtr row_first = make_buf((size_t)(np ? np : 1) * 4);
+  BufPtr word_counts = make_buf((size_t)(n_words ? n_words : 1) * 4);
+  BufPtr prefix = make_buf((size_t)(n_words + 1) * 8);
+  int g = grid_for(n_words, BLOCK / WAVE);
+  if (np) {
+    ProfileScope ps("join_probe_count", key_bytes + np * 4);
+    with_kind(p.jt.kind, [&](auto kt) {
+      k_probe_count<decltype(kt)::value><<<g, BLOCK, 0, r.stream>>>(p.ctx, np, join_type, row_counts->as<uint32_t>(), word_counts->as<uint32_t>(), p.visited, row_first->as<uint32_t>());
+    });
+    DFGPU_HIP(hipGetLastError());
+  }
+  scan_u32(word_counts->as<uint32_t>(), n_words, prefix->as<uint64_t>());
+  const int64_t n_out = (int64_t)read_u64(prefix->as<uint64_t>() + n_words);
+  BufPtr ob = make_buf((size_t)(n_out ? n_out : 1) * 8), op = make_buf((size_t)(n_out ? n_out : 1) * 8);
+  BufPtr om = join_type == DFGPU_JOIN_RIGHT_MARK ? make_buf((size_t)n_out + 64) : nullptr;
+  if (n_out) {
+    ProfileScope ps("join_probe_emit", key_bytes + np * 4 + n_out * 16);
+    with_kind(p.jt.kind, [&](auto kt) {
+      k_probe_emit<decltype(kt)::value><<<g, BLOCK, 0, r.stream>>>(p.ctx, np, join_type, row_counts->as<uint32_t>(), prefix->as<uint64_t>(), ob->as<int64_t>(), op->as<int64_t>(), om ? om->as<uint8_t>() : nullptr, row_first->as<uint32_t>());
+    });
+    DFGPU_HIP(hipGetLastError());
+  }
+  Table out;
+  out.nrows = n_out;
+  const bool build_null_possible = join_type == DFGPU_JOIN_RIGHT || join_type == DFGPU_JOIN_FULL;
+  if (join_type != DFGPU_JOIN_RIGHT_MARK)
+    for (Column& c : gather_columns(p.jt.build, p.bout, ob->as<int64_t>(), n_out, build_null_possible)) out.cols.push_back(std::move(c));
+  for (Column& c : gather_columns(p.probe, p.pout, op->as<int64_t>(), n_out, false)) out.cols.push_back(std::move(c));
+  if (join_type == DFGPU_JOIN_RIGHT_MARK) out.cols.push_back(mark_column(om->as<uint8_t>(), n_out));
+  return out;
+}
+// plan, let the device's answers revise the plan, route
+static Table probe_core(JoinTable& jt, const Table& probe, const std::vector<int>& pk, int join_type, const std::vector<int>& bout, const std::vector<int>& pout,
+                        const uint64_t* row_mask, bool* mask_consumed, const LazyRowFilter* lazy, ProbeHints hints, uint8_t* visited) {
+  ProbeRun p{jt, probe, pk, join_type, bout, pout, row_mask, lazy, mask_consumed, hints, visited, probe.nrows, (probe.nrows + 63) / 64, jt.kind,
+             make_ctx(jt, probe, pk, /*need_build_rows=*/false, /*want_tab=*/false),  // both asked for by the flavour that needs them
+             {}, {}};
+  p.ctx.row_mask = row_mask;
+  ProbePlan& pl = p.plan = plan_probe(p);
+  if (trace_on("join"))   // one line per probe on stderr: what decided the probe flavour
+    fprintf(stderr, "[dfgpu join_probe] np=%lld kind=%d probe_mode=%d fused_ok=%d big_table=%d unclustered=%d grouped_keys_only=%d returned=%d rows_unused=%d row_mask=%d\n",
+            (long long)p.np, jt.kind, jt.probe_mode, pl.fused_ok, pl.big_table, pl.unclustered, pl.grouped_keys_only, pl.try_returned, pl.rows_unused, row_mask != nullptr);
+  if (pl.try_returned) {
+    p.need_mask();
+    plan_after_lookup(pl, p, grouped_probe_lookup(jt, probe, pk[0], bout, p.row_mask, p.rp));
+  }
+  if (pl.returned) {
+    p.kind = KIND_RETURNED;
+    p.ctx.ret_dest = p.rp.dest->as<uint32_t>();
+    p.ctx.ret_rec = p.rp.rec->as<uint8_t>();
+    p.ctx.ret_R = p.rp.R;
+  } else if (!pl.rows_unused && jt.kind == KIND_RANK && jt.rank_needs_perm) {
+    ensure_rank_perm(jt);
+    p.ctx.rank_perm = jt.rank_perm->as<uint32_t>();
+    p.ctx.rank_tab = jt.rank_tab->as<ulonglong2>();
+  }
+  DFGPU_CHECK(!((jt.probe_mode == 2 || jt.probe_mode == 3) && !pl.fused_ok),
+              "single-pass probe requested but not applicable (needs <=1 match per probe row and non-nullable payload)");
+  if (pl.grouped_keys_only) return probe_grouped_keys(p);
+  pl.pred_in_counts = p.lazy != nullptr && pl.use_fused && pl.listed;
+  if (!pl.pred_in_counts) p.need_mask();
+  if (p.row_mask || pl.pred_in_counts) {
+    DFGPU_CHECK(mask_consumed != nullptr, "probe row mask without a fallback");
+    *mask_consumed = pl.use_fused || pl.one_match_path;
     if (!*mask_consumed) return Table{};
-    ctx.row_mask = row_mask;
   }
   // the interleaved rank table: every flavour but the listed one (membership from the bitmap in the counts pass, ranks of the few
   // listed rows from bitmap + prefix) looks every row's rank up through it
-  const bool listed_flavour = use_fused_now && listed && fused_mode == FUSED_PLACED && kind == KIND_RANK;
-  if (!listed_flavour) need_tab();
-  if (use_fused_now && fused_mode != FUSED_PLACED) {
+  if (!(pl.use_fused && pl.listed && p.kind == KIND_RANK)) p.need_tab();
+  if (pl.use_fused && pl.fused_mode != FUSED_PLACED) {
     // single-pass flavours: output columns are allocated for the upper bound (np rows) because the row count is only
     // known when the kernel ends; HBM is sized for that (288 GB)
     size_t free_b = 0, total_b = 0;
     DFGPU_HIP(hipMemGetInfo(&free_b, &total_b));
-    DFGPU_CHECK(np * out_row_bytes <= (int64_t)free_b + r.cached, "single-pass probe: the np-row upper bound of the output does not fit in HBM");
+    DFGPU_CHECK(p.np * pl.out_row_bytes <= (int64_t)free_b + rt().cached, "single-pass probe: the np-row upper bound of the output does not fit in HBM");
   }
+  return pl.use_fused ? probe_fused(p) : pl.first_match ? probe_first_match(p) : pl.single_pass_pairs ? probe_pairs_single(p) : probe_pairs(p);
+}
 
-  if (use_fused_now) {
-    const int64_t tile_words = (int64_t)FUSED_W * (BLOCK / WAVE);
-    const int64_t n_tiles = (n_words + tile_words - 1) / tile_words;
-    const int invert = join_type == DFGPU_JOIN_RIGHT_ANTI;
-    ctx.row_mask = row_mask;
-    BufPtr state = fused_mode == FUSED_LOOKBACK ? make_zero_buf((size_t)n_tiles * 8) : nullptr;
-    BufPtr ctl;   // (made by the flavour that hands it to a kernel: the shared one reports to the host directly and needs none)
-    auto need_ctl = [&]() {
-      if (!ctl) ctl = make_zero_buf(sizeof(FusedCtl));
-      return ctl->as<FusedCtl>();
-    };
-    BufPtr out_words;
-    int64_t n_alloc = np;
-    // ---- speculation for the probe-order output: a foreign-key probe (every row finds its key) needs no counts pass — row i of
-    // the output IS probe row i.  64 K sampled rows that all hit make it worth trying; the kernel verifies every row and the
-    // host starts over with the counts when one disagrees (the reference's order, exec.rs:3349, at the unordered flavour's cost)
-    static thread_local bool no_speculation = false;
-    DevBuf* hit_hint = nullptr;   // where the sample's answer is remembered (all_hit_tag), when it was asked
-    uint64_t hit_tag = 0;
-    // the same probe again, counted: what a speculation that met a row without a partner falls back to
-    auto probe_again_counted = [&](hipEvent_t ea, hipEvent_t eb) {
-      if (hit_hint) hit_hint->all_hit_hint.store(hit_tag, std::memory_order_relaxed);   // (the sample was wrong about these rows: not asked again)
-      if (r.profiling) {
-        std::lock_guard<std::mutex> lk(r.mu);
-        r.recs.push_back(Runtime::Rec{"join_probe_speculation_missed", ea, eb, 0, std::this_thread::get_id()});
-      }
-      {
-        std::lock_guard<std::mutex> lk(jt.mu);
-        jt.info.probe_rows -= np;
-      }
-      out = Table{};   // (the half-made output goes back to the pool first)
-      no_speculation = true;
-      Table again;
-      try {
-        again = join_probe(jt, probe, pk, join_type, bout_in, pout, row_mask, mask_consumed);
-      } catch (...) {
-        no_speculation = false;
-        throw;
-      }
-      no_speculation = false;
-      return again;
-    };
-    bool speculate = false;
-    const bool spec_kind = kind == KIND_RANK || kind == KIND_ARRAY || kind == KIND_FLAT || kind == KIND_FLAT16;
-    // from how many probe rows the sample (a kernel and a blocking read-back) is worth its answer
-    const bool may_sample = !row_mask && !lazy && !invert && !no_speculation && spec_kind && np >= option_int("join.share_probe_min_rows", 1 << 22);
-    // ---- the shared flavour (k_join_probe_shared): when every row hits and the output is in probe order — required by probe_mode
-    // 0 / 1, one admissible order for 3 / 4 — the output's probe-side columns ARE the probe table's columns (immutable, reference-
-    // counted buffers: second owners, as dfgpu_table_select hands out) and only the build-side columns are written.  `listed` resting
-    // on the key-density guess alone does not keep an all-hit probe away: the sample is asked first, and a sample that finds a miss
-    // leaves `listed` and everything below as it was.
-    const bool share_wanted = option_on("join.share_probe", true) && jt.probe_mode != 2 && !returned && (fast_inner || join_type == DFGPU_JOIN_RIGHT_SEMI);
-    if (returned_all_hit && !no_speculation) {
-      speculate = true;   // (not a guess here: the grouped lookup counted its hits; the kernel's per-tile check stays as the safety net)
-    } else if (may_sample && (share_wanted || (fused_mode == FUSED_PLACED && !listed))) {
-      // asked before of these key buffers?  (a kernel and a blocking read-back, 0.04 ms, on every unmasked fused probe otherwise)
-      hit_hint = probe.cols[(size_t)pk[0]].data.get();
-      hit_tag = all_hit_tag(jt, probe, pk, kind);
-      const uint64_t h = hit_hint->all_hit_hint.load(std::memory_order_relaxed);
-      if ((h & ~1ull) == hit_tag) {
-        speculate = (h & 1ull) != 0;
-      } else {
-        constexpr int S = 1024;  // sampled words
-        BufPtr miss = make_zero_buf(4);
-        with_kind_and_key(kind, ctx.pkeys.c[0].type, [&](auto kd, auto kt) {
-          k_sample_all_hit<decltype(kd)::value, decltype(kt)::value><<<S * WAVE / BLOCK, BLOCK, 0, r.stream>>>(ctx, np, std::max<int64_t>(1, n_words / S), S, miss->as<int>());
-        });
-        DFGPU_HIP(hipGetLastError());
-        int m = 0;
-        d2h(&m, miss->ptr, 4);
-        speculate = m == 0;
-        hit_hint->all_hit_hint.store(hit_tag | (speculate ? 1ull : 0ull), std::memory_order_relaxed);
-      }
+static Table join_probe(JoinTable& jt, const Table& probe, const std::vector<int>& pk, int join_type, const std::vector<int>& bout_in,
+                        const std::vector<int>& pout, const uint64_t* row_mask = nullptr, bool* mask_consumed = nullptr, const LazyRowFilter* lazy = nullptr) {
+  if (row_mask) lazy = nullptr;
+  // RightSemi / RightAnti emit probe columns only (joins/utils.rs:1628,1576): build_out_cols given by a C-ABI caller are ignored
+  // on every path — the fused kernel would otherwise gather build rows of unmatched (anti) probe rows
+  const std::vector<int> bout = (join_type == DFGPU_JOIN_RIGHT_SEMI || join_type == DFGPU_JOIN_RIGHT_ANTI) ? std::vector<int>{} : bout_in;
+  DFGPU_CHECK(pk.size() == jt.key_cols.size(), "probe key count differs from build key count");
+  DFGPU_CHECK(probe.device == jt.build.device, "the probe table lives on another device than the join table (move it with dfgpu_table_copy_to_device)");
+  for (int c : bout) DFGPU_CHECK(c >= 0 && c < (int)jt.build.cols.size(), "build output column out of range");
+  for (int c : pout) DFGPU_CHECK(c >= 0 && c < (int)probe.cols.size(), "probe output column out of range");
+  if (jt.kind == KIND_RADIX) return probe_radix(jt, probe, pk, join_type, bout, pout, row_mask || lazy, mask_consumed);   // (counts its rows itself, or join_probe_with_filter does)
+  uint8_t* visited = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(jt.mu);
+    if (needs_visited(join_type) && !jt.visited) {
+      jt.visited = make_zero_buf((size_t)jt.build.nrows + 64);
+      DFGPU_HIP(hipStreamSynchronize(rt().stream));  // zeroed before any other thread's stream marks rows in it
     }
-    const bool shared_now = speculate && share_wanted && !returned_all_hit;
-    // (every other flavour zeroes its control word here, ahead of its counts pass, as ever: the fill is then not what its kernel waits for)
-    if (!shared_now) need_ctl();
-    if (shared_now) {
-      need_tab();   // (a probe `listed` by the guess has not asked for the interleaved rank table yet)
-      JoinCopyCols jc{};
-      jc.key_col = -1;
-      int64_t bytes = key_bytes;   // what this launch moves: the keys once, the build payload once, the build-side output once
-      for (int c : bout) {
-        const Column& sc = jt.build.cols[c];
-        out.cols.push_back(alloc_like(sc, np));
-        jc.src[jc.n] = sc.ptr();
-        jc.dst[jc.n] = out.cols.back().data->ptr;
-        jc.width[jc.n] = type_width(sc.field.type);
-        bytes += (jt.build.nrows + np) * jc.width[jc.n];
-        jc.n++;
-      }
-      jc.n_build = jc.n;
-      // where the kernel reports a miss: the thread's word of pinned host memory, zeroed here (the stream is idle with respect to
-      // it: every earlier probe of this thread waited for its kernel); else the device control word, with its fill and its copy
-      HostFlag* box = option_on("join.probe_host_flag", true) ? thread_host_flag() : nullptr;
-      unsigned* miss_flag = box ? box->dev : &need_ctl()->ticket;
-      if (box) *box->host = 0u;
-      hipEvent_t ea = nullptr, eb = nullptr;
-      if (r.profiling) {
-        for (hipEvent_t* e : {&ea, &eb}) DFGPU_HIP(hipEventCreate(e));
-        DFGPU_HIP(hipEventRecord(ea, r.stream));
-      }
-      with_kind_and_key(kind, ctx.pkeys.c[0].type, [&](auto kd, auto kt) {
-        constexpr int K = decltype(kd)::value, T = decltype(kt)::value;
-        if constexpr (K == KIND_RANK || K == KIND_ARRAY || K == KIND_FLAT || K == KIND_FLAT16) {
-          const int64_t waves = (n_words + SHARED_W - 1) / SHARED_W;
-          const unsigned g = (unsigned)((waves + BLOCK / WAVE - 1) / (BLOCK / WAVE));
-          k_join_probe_shared<K, T, SHARED_W><<<g, BLOCK, 0, r.stream>>>(ctx, jc, np, miss_flag);
-        }
-      });
-      DFGPU_HIP(hipGetLastError());
-      if (r.profiling) DFGPU_HIP(hipEventRecord(eb, r.stream));
-      unsigned missed = 0;   // the one read-back: the output's row count is np without asking
-      if (box) {
-        DFGPU_HIP(hipStreamSynchronize(r.stream));
-        missed = *box->host;
-      } else {
-        d2h(&missed, miss_flag, 4);
-      }
-      if (missed) return probe_again_counted(ea, eb);
-      for (int c : pout) {   // second owners of the probe's buffers; the rows are the same rows, so the statistics stay
-        out.cols.push_back(probe.cols[c]);
-        out.cols.back().length = np;
-      }
-      if (r.profiling) {
-        std::lock_guard<std::mutex> lk(r.mu);
-        r.recs.push_back(Runtime::Rec{want_single ? "join_probe_fused" : "join_probe_placed", ea, eb, bytes, std::this_thread::get_id()});
-        r.recs.push_back(Runtime::Rec{"join_probe_shared_columns", nullptr, nullptr, 0, std::this_thread::get_id()});   // (a label: which path ran; moves nothing)
-      }
-      out.nrows = np;
-      jt.info.output_rows += out.nrows;
-      return out;
-    }
-    speculate = speculate && fused_mode == FUSED_PLACED && !listed;   // (asked for the shared flavour only: nothing else to speculate on)
-    if (fused_mode == FUSED_PLACED && !speculate) {
-      // pass 1: output rows per tile (reads the probe keys only), then the tiles' exclusive prefix
-      BufPtr counts = make_buf((size_t)n_tiles * 4);
-      state = make_buf((size_t)(n_tiles + 1) * 8);
-      if (listed) out_words = make_buf((size_t)n_words * 8);
-      if (kind == KIND_RANK) need_bits();
-      {
-        ProfileScope ps("join_probe_tile_counts", key_bytes + (pred_in_counts ? np * lazy->pred_bytes_per_row : 0));
-        with_kind_and_key(kind, ctx.pkeys.c[0].type, [&](auto kd, auto kt) {
-          constexpr int K = decltype(kd)::value, T = decltype(kt)::value;
-          if constexpr (kind_is_direct<K>()) {
-            const bool nt = option_on("join.counts_nt", true);
-            if (pred_in_counts) {
-              if (nt) k_join_tile_counts<K, T, FUSED_W, true, true><<<(unsigned)n_tiles, BLOCK, 0, r.stream>>>(ctx, np, invert, nullptr, counts->as<uint32_t>(), out_words->as<uint64_t>(), lazy->pred);
-              else k_join_tile_counts<K, T, FUSED_W, true><<<(unsigned)n_tiles, BLOCK, 0, r.stream>>>(ctx, np, invert, nullptr, counts->as<uint32_t>(), out_words->as<uint64_t>(), lazy->pred);
-              return;
-            }
-            if (nt) {
-              k_join_tile_counts<K, T, FUSED_W, false, true><<<(unsigned)n_tiles, BLOCK, 0, r.stream>>>(ctx, np, invert, row_mask, counts->as<uint32_t>(), out_words ? out_words->as<uint64_t>() : nullptr);
-              return;
-            }
-          }
-          k_join_tile_counts<K, T, FUSED_W><<<(unsigned)n_tiles, BLOCK, 0, r.stream>>>(
-              ctx, np, invert, row_mask, counts->as<uint32_t>(), out_words ? out_words->as<uint64_t>() : nullptr);
-        });
-        DFGPU_HIP(hipGetLastError());
-      }
-      scan_u32(counts->as<uint32_t>(), n_tiles, state->as<uint64_t>());
-      n_alloc = (int64_t)read_u64(state->as<uint64_t>() + n_tiles);
-      listed = listed && n_alloc * 4 <= np;  // denser than guessed: the placed kernel streams better than it lists
-      if (!listed) need_tab();
-      if (pred_in_counts && !listed) {
-        // the placed kernel wants a row mask: the counts pass's output words ARE one — (hit & predicate) read as "rows that exist"
-        // selects exactly the rows that come out, for the inverted (anti) probe as well
-        row_mask = out_words->as<uint64_t>();
-        ctx.row_mask = row_mask;
-      }
-    }
-    JoinCopyCols jc{};
-    jc.key_col = -1;
-    int64_t bytes_in = key_bytes, bytes_per_out = 0, bytes_build_once = 0;
-    for (int c : bout) {
-      const Column& sc = jt.build.cols[c];
-      out.cols.push_back(alloc_like(sc, n_alloc));
-      jc.src[jc.n] = sc.ptr();
-      jc.dst[jc.n] = out.cols.back().data->ptr;
-      jc.width[jc.n] = type_width(sc.field.type);
-      if (returned) {  // the column's values came back inside the records
-        jc.src[jc.n] = rp.rec->ptr;
-        jc.ret_mul[jc.n] = rp.mul[(size_t)jc.n];
-        jc.ret_add[jc.n] = rp.add[(size_t)jc.n];
-      }
-      bytes_per_out += jc.width[jc.n];
-      bytes_build_once += jt.build.nrows * jc.width[jc.n];
-      jc.n++;
-    }
-    jc.n_build = jc.n;
-    for (int c : pout) {
-      const Column& sc = probe.cols[c];
-      out.cols.push_back(alloc_like(sc, n_alloc));
-      jc.src[jc.n] = sc.ptr();
-      jc.dst[jc.n] = out.cols.back().data->ptr;
-      jc.width[jc.n] = type_width(sc.field.type);
-      bool is_key = false;
-      for (int k : pk) is_key |= k == c;
-      if (!is_key) bytes_in += np * jc.width[jc.n];  // a key column that is also payload is read once
-      if (is_key && (kind == KIND_ARRAY || kind == KIND_RANK) && pk.size() == 1 && jc.key_col < 0 && !sc.validity) jc.key_col = jc.n;
-      bytes_per_out += jc.width[jc.n];
-      jc.n++;
-    }
-    hipEvent_t ea = nullptr, eb = nullptr;
-    if (r.profiling) {
-      DFGPU_HIP(hipEventCreate(&ea));
-      DFGPU_HIP(hipEventCreate(&eb));
-      DFGPU_HIP(hipEventRecord(ea, r.stream));
-    }
-    int64_t n_out = n_alloc;
-    if (fused_mode != FUSED_PLACED || n_alloc > 0) {
-      // look-back: persistent workgroups pulling tickets; unordered / placed: one workgroup per tile
-      const unsigned g = fused_mode == FUSED_LOOKBACK ? (unsigned)std::min<int64_t>(n_tiles, (int64_t)r.num_cus * 8) : (unsigned)n_tiles;
-      uint64_t* st = state ? state->as<uint64_t>() : nullptr;
-      FusedCtl* const d_ctl = need_ctl();
-      auto launch = [&](auto kern) { kern<<<g, BLOCK, 0, r.stream>>>(ctx, jc, np, invert, st, d_ctl, row_mask); };
-      with_kind_and_key(kind, ctx.pkeys.c[0].type, [&](auto kd, auto kt) {
-        constexpr int K = decltype(kd)::value, T = decltype(kt)::value;
-        constexpr bool KR = kind_is_direct<K>();  // the direct-address kinds hold the one integer key in registers
-        if constexpr (KR) {
-          if (listed) {
-            // (sparse: fewer than one row in `join.listed_sparse_den` comes out)
-            const int64_t den = option_int("join.listed_sparse_den", 32);   // (0: never)
-            if (den > 0 && n_alloc * den <= np) {
-              const int64_t groups = (n_words + EL_WORDS_SPARSE - 1) / EL_WORDS_SPARSE;
-              k_join_emit_listed<K, T, EL_WORDS_SPARSE><<<(unsigned)groups, BLOCK, 0, r.stream>>>(ctx, jc, np, out_words->as<uint64_t>(), st, (int)(EL_WORDS_SPARSE / tile_words));
-            } else {
-              const int64_t groups = (n_words + EL_WORDS - 1) / EL_WORDS;
-              k_join_emit_listed<K, T, EL_WORDS><<<(unsigned)groups, BLOCK, 0, r.stream>>>(ctx, jc, np, out_words->as<uint64_t>(), st, (int)(EL_WORDS / tile_words));
-            }
-            return;
-          }
-        }
-        if (fused_mode == FUSED_LOOKBACK) launch(k_join_probe_fused<K, T, FUSED_W, FUSED_LOOKBACK, false>);
-        else if (fused_mode == FUSED_PLACED) {
-          if (KR && jc.key_col >= 0) launch(k_join_probe_fused<K, T, FUSED_W, FUSED_PLACED, KR>);
-          else launch(k_join_probe_fused<K, T, FUSED_W, FUSED_PLACED, false>);
-        } else {
-          if (KR && jc.key_col >= 0) launch(k_join_probe_fused<K, T, FUSED_W, FUSED_UNORDERED, KR>);
-          else launch(k_join_probe_fused<K, T, FUSED_W, FUSED_UNORDERED, false>);
-        }
-      });
-      DFGPU_HIP(hipGetLastError());
-      if (r.profiling) DFGPU_HIP(hipEventRecord(eb, r.stream));
-      if (fused_mode != FUSED_PLACED) n_out = (int64_t)read_u64(reinterpret_cast<const uint64_t*>(&d_ctl->total));
-      if (speculate) {
-        unsigned missed = 0;
-        d2h(&missed, &d_ctl->ticket, 4);
-        if (missed) return probe_again_counted(ea, eb);   // some probe row has no partner after all
-      }
-    } else if (r.profiling) {
-      DFGPU_HIP(hipEventRecord(eb, r.stream));
-    }
-    // algorithmic bytes of this launch (SURVEY 8d config 3 ii): every referenced probe column once, the build payload
-    // columns once, the output written once (re-reads of build rows matched by several probe rows, table words, tile
-    // state are overhead); known only now that n_out is
-    if (r.profiling) {
-      std::lock_guard<std::mutex> lk(r.mu);
-      r.recs.push_back(Runtime::Rec{listed ? "join_probe_listed" : fused_mode == FUSED_PLACED ? "join_probe_placed" : "join_probe_fused", ea, eb,
-                                    bytes_in + (n_out > 0 ? bytes_build_once : 0) + n_out * bytes_per_out, std::this_thread::get_id()});
-    }
-    out.nrows = n_out;
-    for (Column& c : out.cols) c.length = n_out;
-  } else if (np > 0 && (probe_side_only || (build_side_only && jt.keys_unique) || fast_inner)) {
-  // LeftSemi/LeftAnti/LeftMark must mark EVERY matching build row: first-match suffices only for unique keys
-    // ---- at most one match per probe row
-    BufPtr mask = make_buf(bitmap_bytes(np));
-    BufPtr first = fast_inner ? make_buf((size_t)np * 4) : nullptr;
-    {
-      ProfileScope ps("join_probe_lookup", key_bytes);  // algorithmic: the probe keys (table reads / match ids are overhead)
-      int g = grid_for(n_words, (BLOCK / WAVE) * PROBE_UNROLL);
-      int invert = join_type == DFGPU_JOIN_RIGHT_ANTI;
-      with_kind_and_key(jt.kind, ctx.pkeys.c[0].type, [&](auto kd, auto kt) {
-        k_probe_first<decltype(kd)::value, decltype(kt)::value><<<g, BLOCK, 0, r.stream>>>(ctx, np, invert, first ? first->as<uint32_t>() : nullptr,
-                                                                                           mask->as<uint64_t>(), visited);
-      });
-      DFGPU_HIP(hipGetLastError());
-    }
-    if (probe_side_only) {
-      out = compact_table(probe, pout, mask->as<uint64_t>(), nullptr);
-    } else if (build_side_only) {
-      out.nrows = 0;  // emitted by dfgpu_join_emit_unmatched
-      for (int c : bout) out.cols.push_back(alloc_like(jt.build.cols[c], 0));
-    } else {
-      BufPtr prefix = make_buf((size_t)(n_words + 1) * 8);
-      scan_mask_popcounts(mask->as<uint64_t>(), nullptr, np, prefix->as<uint64_t>());
-      const int64_t n_out = (int64_t)read_u64(prefix->as<uint64_t>() + n_words);
-      out.nrows = n_out;
-      JoinCopyCols jc{};
-      // algorithmic bytes: probe payload read once, build payload read per output row, output
-      // written once (mask / match-id traffic is overhead and not counted)
-      int64_t bytes = 0;
-      for (int c : bout) {
-        const Column& sc = jt.build.cols[c];
-        out.cols.push_back(alloc_like(sc, n_out));
-        jc.src[jc.n] = sc.ptr();
-        jc.dst[jc.n] = out.cols.back().data->ptr;
-        jc.width[jc.n] = type_width(sc.field.type);
-        bytes += 2 * n_out * jc.width[jc.n];
-        jc.n++;
-      }
-      jc.n_build = jc.n;
-      for (int c : pout) {
-        const Column& sc = probe.cols[c];
-        out.cols.push_back(alloc_like(sc, n_out));
-        jc.src[jc.n] = sc.ptr();
-        jc.dst[jc.n] = out.cols.back().data->ptr;
-        jc.width[jc.n] = type_width(sc.field.type);
-        bytes += (np + n_out) * jc.width[jc.n];
-        jc.n++;
-      }
-      if (n_out > 0 && jc.n > 0) {
-        ProfileScope ps("join_probe_materialize", bytes);
-        k_join_materialize<<<grid_for(n_words, (BLOCK / WAVE) * PROBE_UNROLL), BLOCK, 0, r.stream>>>(jc, mask->as<uint64_t>(), prefix->as<uint64_t>(),
-                                                                                                      first->as<uint32_t>(), np);
-        DFGPU_HIP(hipGetLastError());
-      }
-    }
-  } else if (single_pass_pairs) {
-    // ---- general M:N path in one pass (flat tables, INNER, order unobserved): sample -> pairs at a cursor -> gathers
-    constexpr int64_t SAMPLE = 1 << 16;
-    const int64_t every = std::max<int64_t>(1, np / SAMPLE), n_sample = (np + every - 1) / every;
-    BufPtr ctl = make_zero_buf(16);
-    with_kind(jt.kind, [&](auto kt) {
-      constexpr int K = decltype(kt)::value;
-      if constexpr (kind_is_flat<K>()) k_probe_pairs_sample<K><<<grid_for(n_sample, BLOCK), BLOCK, 0, r.stream>>>(ctx, np, every, n_sample, ctl->as<unsigned long long>());
-    });
-    unsigned long long seen = 0;
-    d2h(&seen, ctl->ptr, 8);
-    // (the sample's pairs scaled to the probe side, a quarter more and a constant: an underestimate costs one more pass at the exact size)
-    unsigned long long capacity = (unsigned long long)((double)seen * (double)np / (double)n_sample * 1.25) + (1ull << 16);
-    BufPtr ob, op;
-    unsigned long long total = 0;
-    for (int attempt = 0; attempt < 2; attempt++) {
-      ob = make_buf((size_t)capacity * 8);
-      op = make_buf((size_t)capacity * 8);
-      DFGPU_HIP(hipMemsetAsync(ctl->ptr, 0, 16, r.stream));
-      {
-        ProfileScope ps("join_probe_pairs_single", key_bytes + (int64_t)capacity * 16);
-        const int g = (int)std::min<int64_t>((n_words + PROBE_UNROLL * (BLOCK / WAVE) - 1) / (PROBE_UNROLL * (BLOCK / WAVE)), (int64_t)r.num_cus * 16);
-        with_kind(jt.kind, [&](auto kt) {
-          constexpr int K = decltype(kt)::value;
-          if constexpr (kind_is_flat<K>()) k_probe_pairs_single<K><<<g, BLOCK, 0, r.stream>>>(ctx, np, ctl->as<unsigned long long>(), capacity, ob->as<int64_t>(), op->as<int64_t>());
-        });
-        DFGPU_HIP(hipGetLastError());
-      }
-      d2h(&total, ctl->ptr, 8);
-      if (total <= capacity) break;
-      DFGPU_CHECK(attempt == 0, "join: the single-pass probe overflowed a buffer of its exact size");
-      capacity = total;   // (the cursor counted every pair: the second try fits)
-    }
-    const int64_t n_out = (int64_t)total;
-    out.nrows = n_out;
-    for (Column& c : gather_columns(jt.build, bout, ob->as<int64_t>(), n_out, false)) out.cols.push_back(std::move(c));
-    for (Column& c : gather_columns(probe, pout, op->as<int64_t>(), n_out, false)) out.cols.push_back(std::move(c));
-  } else {
-    // ---- general M:N path: counts -> scan -> pairs -> gathers
-    BufPtr row_counts = make_buf((size_t)(np ? np : 1) * 4);
-    BufPtr row_first = make_buf((size_t)(np ? np : 1) * 4);
-    BufPtr word_counts = make_buf((size_t)(n_words ? n_words : 1) * 4);
-    BufPtr prefix = make_buf((size_t)(n_words + 1) * 8);
-    int g = grid_for(n_words, BLOCK / WAVE);
-    if (np) {
-      ProfileScope ps("join_probe_count", key_bytes + np * 4);
-      with_kind(jt.kind, [&](auto kt) {
-        k_probe_count<decltype(kt)::value><<<g, BLOCK, 0, r.stream>>>(ctx, np, join_type, row_counts->as<uint32_t>(), word_counts->as<uint32_t>(), visited, row_first->as<uint32_t>());
-      });
-      DFGPU_HIP(hipGetLastError());
-    }
-    scan_u32(word_counts->as<uint32_t>(), n_words, prefix->as<uint64_t>());
-    const int64_t n_out = (int64_t)read_u64(prefix->as<uint64_t>() + n_words);
-    BufPtr ob = make_buf((size_t)(n_out ? n_out : 1) * 8), op = make_buf((size_t)(n_out ? n_out : 1) * 8);
-    BufPtr om = join_type == DFGPU_JOIN_RIGHT_MARK ? make_buf((size_t)n_out + 64) : nullptr;
-    if (n_out) {
-      ProfileScope ps("join_probe_emit", key_bytes + np * 4 + n_out * 16);
-      with_kind(jt.kind, [&](auto kt) {
-        k_probe_emit<decltype(kt)::value><<<g, BLOCK, 0, r.stream>>>(ctx, np, join_type, row_counts->as<uint32_t>(), prefix->as<uint64_t>(), ob->as<int64_t>(), op->as<int64_t>(), om ? om->as<uint8_t>() : nullptr, row_first->as<uint32_t>());
-      });
-      DFGPU_HIP(hipGetLastError());
-    }
-    out.nrows = n_out;
-    const bool build_null_possible = join_type == DFGPU_JOIN_RIGHT || join_type == DFGPU_JOIN_FULL;
-    if (join_type != DFGPU_JOIN_RIGHT_MARK)
-      for (Column& c : gather_columns(jt.build, bout, ob->as<int64_t>(), n_out, build_null_possible)) out.cols.push_back(std::move(c));
-    for (Column& c : gather_columns(probe, pout, op->as<int64_t>(), n_out, false)) out.cols.push_back(std::move(c));
-    if (join_type == DFGPU_JOIN_RIGHT_MARK) out.cols.push_back(mark_column(om->as<uint8_t>(), n_out));
+    if (needs_visited(join_type)) visited = jt.visited->as<uint8_t>();
+    jt.info.probe_rows += probe.nrows;
   }
+  Table out = probe_core(jt, probe, pk, join_type, bout, pout, row_mask, mask_consumed, lazy, ProbeHints{}, visited);
+  std::lock_guard<std::mutex> lk(jt.mu);
   jt.info.output_rows += out.nrows;
   return out;
 }
+
 
 // HashJoinExec with a JoinFilter: the general (pairs) path with the filter between pair generation and the
 // per-JoinType adjustment.  Not a tuned path: pairs and the intermediate batch are materialised.

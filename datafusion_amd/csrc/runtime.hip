@@ -385,6 +385,33 @@ ProfileScope::~ProfileScope() {
   std::lock_guard<std::mutex> lk(r.mu);   // scan threads decode column chunks concurrently (parquet.hip)
   r.recs.push_back({name, a, b, bytes, std::this_thread::get_id()});
 }
+LateRecord::LateRecord() {
+  Runtime& r = rt();
+  if (!r.profiling) return;
+  DFGPU_HIP(hipEventCreate(&a));
+  DFGPU_HIP(hipEventCreate(&b));
+  DFGPU_HIP(hipEventRecord(a, r.stream));
+}
+LateRecord::~LateRecord() {
+  if (a) (void)hipEventDestroy(a);
+  if (b) (void)hipEventDestroy(b);
+}
+void LateRecord::stop() {
+  if (a) DFGPU_HIP(hipEventRecord(b, rt().stream));
+}
+void LateRecord::record(const char* name, int64_t algorithmic_bytes) {
+  if (!a) return;
+  Runtime& r = rt();
+  std::lock_guard<std::mutex> lk(r.mu);
+  r.recs.push_back({name, a, b, algorithmic_bytes, std::this_thread::get_id()});
+  a = b = nullptr;
+}
+void LateRecord::label(const char* name) {
+  Runtime& r = rt();
+  if (!r.profiling) return;
+  std::lock_guard<std::mutex> lk(r.mu);
+  r.recs.push_back({name, nullptr, nullptr, 0, std::this_thread::get_id()});
+}
 
 void Runtime::collect() {
   if (recs.empty()) return;
