@@ -126,8 +126,14 @@ SYMBOLS = [
     "dfgpu_table_retain", "dfgpu_table_export_device", "dfgpu_table_import_device",
     "dfgpu_cache_create", "dfgpu_cache_free", "dfgpu_cache_get", "dfgpu_cache_put", "dfgpu_cache_clear", "dfgpu_cache_get_stats", "dfgpu_jit_cache_stats", "dfgpu_join_contains", "dfgpu_exchange_join_visited", "dfgpu_exchange_range",
     "dfgpu_agg_create_grouping_sets", "dfgpu_ipc_open", "dfgpu_ipc_close", "dfgpu_ipc_info", "dfgpu_ipc_column", "dfgpu_ipc_batch_rows", "dfgpu_ipc_read_batch",
-    "dfgpu_nested_loop_join",
+    "dfgpu_nested_loop_join", "dfgpu_range_join",
 ]
+
+# argument types of the entry points that are also called with plain Python values (None for an absent column array)
+ARGTYPES = {
+    "dfgpu_range_join": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_int,
+                         C.POINTER(C.c_void_p)],
+}
 
 _lib = None
 _initialised_device = None
@@ -146,6 +152,8 @@ def load() -> C.CDLL:
         _lib.dfgpu_stream.restype = C.c_void_p
         for name in SYMBOLS:
             getattr(_lib, name)  # AttributeError here = header/library mismatch
+        for name, argtypes in ARGTYPES.items():
+            getattr(_lib, name).argtypes = argtypes
     return _lib
 
 

@@ -9,6 +9,9 @@
 //
 // Output order (include/dfgpu.h): passing pairs in right-row-major order, then the unmatched right rows, then the
 // unmatched left rows; the one-sided types in their side's row order.
+//
+// Below it, sharing the tail: the range join (dfgpu_range_join) — range conditions on one right column by sorting that
+// column and searching the bounds, without the pair space.
 #include "internal.hpp"
 #include "rowprog_host.hpp"
 
@@ -472,6 +475,320 @@ Table nested_loop_join(const Table& left, const Table& right, int jt, const dfgp
   return nlj_materialised(left, right, jt, jf, lout, rout);
 }
 
+// ===================================================================================================================== range join
+// dfgpu_range_join (ABI 20): `a <(=) x AND x <(=) b` over one right column x without the pair space.  The non-NULL x
+// are sorted once as (orderable u64 key, row id) pairs; a left row's matches are then ONE run [lo, hi) of the sorted order, found by
+// two binary searches (k_rj_bounds).  The right rows some run covers come from a difference array (+1 at lo, -1 at hi) and its scan
+// (k_rj_cover) — no pair is enumerated for the six one-sided types and the unmatched tails.  The pair types expand the runs into
+// (left row, right row) ids with the work split over OUTPUT SLOTS (k_rj_expand), and everything ends in nlj_tail above.
+constexpr int RJ_TILE = DFGPU_RANGE_JOIN_TILE;
+static_assert(RJ_TILE % BLOCK == 0 && RJ_TILE <= 65536, "a workgroup writes whole rounds of its lanes; tile-relative offsets are staged as u32");
+// sorted keys every workgroup of k_rj_bounds stages in LDS: every stride-th key, so that the first 11 levels of each search are LDS
+// reads.  16 KiB of the CU's 160 KiB: ten workgroups' staging fit, more than the eight 4-wave workgroups the 32-wave cap lets a CU hold,
+// so the staging never lowers the occupancy.
+constexpr int RJ_SAMPLES = 2048;
+enum RjType : int { RJ_I32 = 0, RJ_U32 = 1, RJ_I64 = 2, RJ_U64 = 3, RJ_F64 = 4 };
+
+// value i of a key column as a u64 whose unsigned order is the expression layer's order of the type: signed values sign-extended with
+// bit 63 flipped; Float64 by the total order of its bits (negative: every bit flipped, else the sign bit)
+template <int T>
+__device__ __forceinline__ uint64_t rj_ordered(const void* d, int64_t i) {
+  if (T == RJ_I32) return (uint64_t)(int64_t)((const int32_t*)d)[i] ^ (1ull << 63);
+  if (T == RJ_U32) return ((const uint32_t*)d)[i];
+  if (T == RJ_I64) return ((const uint64_t*)d)[i] ^ (1ull << 63);
+  if (T == RJ_U64) return ((const uint64_t*)d)[i];
+  const uint64_t b = ((const uint64_t*)d)[i];
+  return b ^ ((uint64_t)((int64_t)b >> 63) | (1ull << 63));
+}
+
+// first position in [lo, hi) of the ascending `keys` whose key is >= q (UPPER: > q); hi when there is none
+template <bool UPPER, class E, class Q>
+__device__ __forceinline__ uint32_t rj_search(const E* keys, uint32_t lo, uint32_t hi, Q q) {
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    const Q k = keys[mid];
+    if (UPPER ? k <= q : k < q) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// the non-NULL rows of x, compacted in row order: key = ordered(x) - base, idx = the row (idx null: no NULLs, the position is the row)
+template <int T>
+__global__ __launch_bounds__(BLOCK) void k_rj_keys(const void* __restrict__ x, const uint64_t* __restrict__ valid, const uint64_t* __restrict__ prefix, int64_t n,
+                                                   uint64_t base, uint64_t* __restrict__ key, uint32_t* __restrict__ idx) {
+  for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
+    int64_t pos = i;
+    if (valid) {
+      const uint64_t w = valid[i >> 6];
+      if (!((w >> (i & 63)) & 1ull)) continue;
+      pos = (int64_t)prefix[i >> 6] + __popcll(w & ((1ull << (i & 63)) - 1ull));
+      idx[pos] = (uint32_t)i;
+    }
+    key[pos] = rj_ordered<T>(x, i) - base;
+  }
+}
+
+struct RjBounds {
+  const void* a;               // lower bound column (null: none) and its validity
+  const uint64_t* a_valid;
+  const void* b;               // upper bound column (null: none) and its validity
+  const uint64_t* b_valid;
+  int lower_inclusive, upper_inclusive;
+  int64_t nl;
+  const uint64_t* keys;        // [m] ascending: ordered(x) - base, every one <= span
+  uint32_t m, stride, ns;      // the ns staged keys are keys[j * stride]
+  uint64_t base, span;
+  uint32_t* lo;                // [nl] start of the row's run in the sorted order
+  uint32_t* count;             // [nl] its length
+  uint8_t* visited;            // [nl] count != 0
+  int32_t* diff;               // [m + 1] zeroed: +1 at lo, -1 at hi of every non-empty run; null when no right-side flag is needed
+};
+
+// position of left value `l` of `col` among the sorted keys: lower_bound, or upper_bound when `upper`
+template <int T>
+__device__ __forceinline__ uint32_t rj_position(const RjBounds& g, const uint64_t* s_keys, const void* col, int64_t l, bool upper) {
+  const uint64_t v = rj_ordered<T>(col, l);
+  if (v < g.base) return 0;
+  const uint64_t q = v - g.base;
+  if (q > g.span) return g.m;
+  // staged keys before position j compare on q's near side, so the answer lies in ((j - 1) * stride, j * stride]
+  const uint32_t j = upper ? rj_search<true>(s_keys, 0u, g.ns, q) : rj_search<false>(s_keys, 0u, g.ns, q);
+  if (j == 0) return 0;
+  const uint32_t lo = (j - 1) * g.stride + 1;
+  const uint32_t hi = (uint64_t)j * g.stride < (uint64_t)g.m ? j * g.stride : g.m;
+  return upper ? rj_search<true>(g.keys, lo, hi, q) : rj_search<false>(g.keys, lo, hi, q);
+}
+
+// one add per wave for the lanes that share the first adding lane's position (one x value matched by every left row would otherwise put
+// every lane's atomic on one address), one per lane for the others.  Integer adds: the sums do not depend on arrival order.
+__device__ __forceinline__ void rj_diff_add(int32_t* diff, bool on, uint32_t pos, int32_t delta) {
+  const uint64_t adders = ballot64(on);
+  if (!adders) return;
+  const int leader = __builtin_ctzll(adders);
+  const uint32_t lead_pos = (uint32_t)__shfl((int)pos, leader, 64);
+  const uint64_t same = ballot64(on && pos == lead_pos);
+  if ((int)lane_id() == leader) atomicAdd(diff + pos, delta * (int32_t)__popcll(same));
+  else if (on && pos != lead_pos) atomicAdd(diff + pos, delta);
+}
+
+// one lane per left row (coalesced loads of a / b and their validity words)
+template <int T>
+__global__ __launch_bounds__(BLOCK) void k_rj_bounds(const RjBounds g) {
+  __shared__ uint64_t s_keys[RJ_SAMPLES];
+  for (uint32_t j = threadIdx.x; j < g.ns; j += BLOCK) s_keys[j] = g.keys[(uint64_t)j * g.stride];
+  __syncthreads();
+  for (int64_t base = (int64_t)blockIdx.x * BLOCK; base < g.nl; base += (int64_t)gridDim.x * BLOCK) {  // (wave-uniform: rj_diff_add votes)
+    const int64_t l = base + threadIdx.x;
+    const bool in = l < g.nl;
+    bool bounded = in;
+    uint32_t lo = 0, hi = g.m;
+    if (in && g.a) {
+      if (g.a_valid && !bit_at(g.a_valid, l)) bounded = false;
+      else lo = rj_position<T>(g, s_keys, g.a, l, !g.lower_inclusive);
+    }
+    if (bounded && g.b) {
+      if (g.b_valid && !bit_at(g.b_valid, l)) bounded = false;
+      else hi = rj_position<T>(g, s_keys, g.b, l, g.upper_inclusive != 0);
+    }
+    const uint32_t cnt = bounded && hi > lo ? hi - lo : 0u;
+    if (in) {
+      g.lo[l] = lo;
+      g.count[l] = cnt;
+      g.visited[l] = cnt ? 1 : 0;
+    }
+    if (g.diff) {
+      rj_diff_add(g.diff, cnt != 0, lo, 1);
+      rj_diff_add(g.diff, cnt != 0, hi, -1);
+    }
+  }
+}
+
+// sorted position p is covered by cover[p + 1] runs (the exclusive prefix of the difference array, low 32 bits: its -1 entries were
+// summed as 2^32 - 1); the hit byte goes to the row at that position
+__global__ __launch_bounds__(BLOCK) void k_rj_cover(const uint64_t* __restrict__ cover, const uint32_t* __restrict__ perm, uint32_t m, uint8_t* __restrict__ hit) {
+  for (int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x; p < m; p += (int64_t)gridDim.x * BLOCK)
+    if ((int32_t)(uint32_t)cover[p + 1] > 0) hit[perm[p]] = 1;
+}
+
+struct RjExpand {
+  const uint64_t* offsets;     // [nl + 1] exclusive prefix of the runs' lengths = the first output slot of every left row
+  const uint32_t* lo;          // [nl]
+  const uint32_t* perm;        // [m] right row at a sorted position
+  uint32_t nl;
+  int64_t total;
+  int64_t* out_l;
+  int64_t* out_r;
+};
+
+// A workgroup owns RJ_TILE consecutive output slots whatever rows they belong to: one left row that matches everything is written by
+// as many workgroups as a million rows with one match each, and rows without a match cost nothing.  The tile's first and last row are
+// found in the offsets; when the rows between them are at most RJ_TILE their offsets are staged (relative to the tile) and every slot
+// finds its row in LDS, else (many rows without a match in between) in the offsets themselves.  Stores are coalesced: lane t writes
+// slots t, t + BLOCK, ...
+__global__ __launch_bounds__(BLOCK) void k_rj_expand(const RjExpand g) {
+  __shared__ uint32_t s_off[RJ_TILE];
+  __shared__ uint32_t s_row[2];
+  const int64_t n_tiles = (g.total + RJ_TILE - 1) / RJ_TILE;
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const int64_t t0 = tile * RJ_TILE, t1 = t0 + RJ_TILE < g.total ? t0 + RJ_TILE : g.total;
+    // the row of slot j is the first l with offsets[l + 1] > j
+    if (threadIdx.x < 2) s_row[threadIdx.x] = rj_search<true>(g.offsets + 1, 0u, g.nl, (uint64_t)(threadIdx.x ? t1 - 1 : t0));
+    __syncthreads();
+    const uint32_t r0 = s_row[0], nrows = s_row[1] - r0 + 1;
+    const bool staged = nrows <= (uint32_t)RJ_TILE;
+    if (staged)
+      for (uint32_t i = threadIdx.x; i < nrows; i += BLOCK) {
+        const uint64_t o = g.offsets[(uint64_t)r0 + 1 + i] - (uint64_t)t0;
+        s_off[i] = o < (uint64_t)RJ_TILE ? (uint32_t)o : (uint32_t)RJ_TILE;
+      }
+    __syncthreads();
+    for (int64_t j = t0 + threadIdx.x; j < t1; j += BLOCK) {
+      const uint32_t l = r0 + (staged ? rj_search<true>(s_off, 0u, nrows, (uint32_t)(j - t0)) : rj_search<true>(g.offsets + 1 + r0, 0u, nrows, (uint64_t)j));
+      g.out_l[j] = l;
+      g.out_r[j] = g.perm[g.lo[l] + (uint32_t)((uint64_t)j - g.offsets[l])];
+    }
+    __syncthreads();  // s_row / s_off are rewritten for the next tile
+  }
+}
+
+namespace {
+
+int rj_type(int t) {
+  switch (t) {
+    case DFGPU_INT32: case DFGPU_DATE32: return RJ_I32;
+    case DFGPU_UINT32: return RJ_U32;
+    case DFGPU_INT64: return RJ_I64;
+    case DFGPU_UINT64: return RJ_U64;
+    case DFGPU_FLOAT64: return RJ_F64;
+  }
+  return -1;
+}
+template <class F>
+void with_rj_type(int t, F&& f) {
+  switch (t) {
+    case RJ_I32: f(std::integral_constant<int, RJ_I32>{}); break;
+    case RJ_U32: f(std::integral_constant<int, RJ_U32>{}); break;
+    case RJ_I64: f(std::integral_constant<int, RJ_I64>{}); break;
+    case RJ_U64: f(std::integral_constant<int, RJ_U64>{}); break;
+    default: f(std::integral_constant<int, RJ_F64>{}); break;
+  }
+}
+void rj_check_key(const Column& c) {
+  DFGPU_CHECK(!c.dict, "a range join key that is dictionary-encoded is not supported on the GPU path");
+  DFGPU_CHECK(rj_type(c.field.type) >= 0, "a range join key of a type other than Int32, Int64, Date32, UInt32, UInt64 or Float64 is not supported on the GPU path");
+}
+
+}  // namespace
+
+Table range_join(const Table& left, const Table& right, int jt, int x_col, int a_col, bool a_inclusive, int b_col, bool b_inclusive, const std::vector<int>& lout,
+                 const std::vector<int>& rout) {
+  DFGPU_CHECK(left.device == right.device, "the right table lives on another device than the left table (move it with dfgpu_table_copy_to_device)");
+  for (int c : lout) DFGPU_CHECK(c >= 0 && c < (int)left.cols.size(), "left output column out of range");
+  for (int c : rout) DFGPU_CHECK(c >= 0 && c < (int)right.cols.size(), "right output column out of range");
+  DFGPU_CHECK(a_col >= 0 || b_col >= 0, "a range join needs a lower or an upper bound");
+  DFGPU_CHECK(x_col >= 0 && x_col < (int)right.cols.size(), "range join key column out of range");
+  DFGPU_CHECK(a_col < (int)left.cols.size() && b_col < (int)left.cols.size(), "range join bound column out of range");
+  const Column& x = right.cols[x_col];
+  const Column* a = a_col >= 0 ? &left.cols[a_col] : nullptr;
+  const Column* b = b_col >= 0 ? &left.cols[b_col] : nullptr;
+  rj_check_key(x);
+  if (a) rj_check_key(*a);
+  if (b) rj_check_key(*b);
+  DFGPU_CHECK((!a || a->field.type == x.field.type) && (!b || b->field.type == x.field.type), "a range join over keys of different types is not supported on the GPU path");
+  const int64_t nl = left.nrows, nr = right.nrows;
+  DFGPU_CHECK(nl < ((int64_t)1 << 31) && nr < ((int64_t)1 << 31), "a range join side of 2^31 rows or more is not supported on the GPU path");
+
+  Runtime& r = rt();
+  const int T = rj_type(x.field.type), w = type_width(x.field.type);
+  const bool right_flags = jt == DFGPU_JOIN_RIGHT || jt == DFGPU_JOIN_FULL || right_one_sided(jt);
+  NljMatches M;
+  M.hit = make_zero_buf((size_t)nr + 64);
+  M.visited = make_zero_buf((size_t)nl + 64);
+  BufPtr prefix, key, perm, lo, counts, offsets;
+  int64_t m = 0, n_pass = 0;
+  if (nl && nr) {
+    // ---- keys: the non-NULL x as (ordered key - its minimum, row), sorted by the bits the span needs
+    m = nr;
+    if (x.validity) {
+      const int64_t nw = (nr + 63) / 64;
+      prefix = make_buf((size_t)(nw + 1) * 8);
+      scan_mask_popcounts(x.valid_words(), nullptr, nr, prefix->as<uint64_t>());
+      m = (int64_t)read_u64(prefix->as<uint64_t>() + nw);
+    }
+  }
+  if (m) {
+    uint64_t base = 0, span = ~0ull;
+    if (T != RJ_U64 && T != RJ_F64) {  // (column_stats keeps signed 64-bit bounds: not UInt64's, and Float64 has no integer order)
+      const ColStats st = column_stats(const_cast<Column&>(x), nr);  // fills the column's shared cache; the rows do not change
+      const uint64_t flip = T == RJ_U32 ? 0ull : 1ull << 63;
+      base = (uint64_t)st.min ^ flip;
+      span = ((uint64_t)st.max ^ flip) - base;  // in u64: INT64_MAX - INT64_MIN is 2^64 - 1
+    }
+    const int nbits = span ? 64 - __builtin_clzll(span) : 0;
+    key = make_buf((size_t)m * 8);
+    if (x.validity) perm = make_buf((size_t)m * 4);
+    {
+      ProfileScope ps("rangejoin_keys", nr * w + m * (x.validity ? 12 : 8));
+      with_rj_type(T, [&](auto t) {
+        k_rj_keys<decltype(t)::value><<<grid_for(nr, BLOCK), BLOCK, 0, r.stream>>>(x.ptr(), x.valid_words(), prefix ? prefix->as<uint64_t>() : nullptr, nr, base,
+                                                                                  key->as<uint64_t>(), perm ? perm->as<uint32_t>() : nullptr);
+      });
+      DFGPU_HIP(hipGetLastError());
+    }
+    radix_sort_pairs(key, perm, m, 0, nbits);  // stable: equal x keep ascending row order
+
+    // ---- bounds: every left row's run of the sorted order
+    lo = make_buf((size_t)nl * 4);
+    counts = make_buf((size_t)nl * 4);
+    BufPtr diff = right_flags ? make_zero_buf((size_t)(m + 1) * 4) : nullptr;
+    RjBounds g{};
+    g.a = a ? a->ptr() : nullptr;
+    g.a_valid = a ? a->valid_words() : nullptr;
+    g.b = b ? b->ptr() : nullptr;
+    g.b_valid = b ? b->valid_words() : nullptr;
+    g.lower_inclusive = a_inclusive;
+    g.upper_inclusive = b_inclusive;
+    g.nl = nl;
+    g.keys = key->as<uint64_t>();
+    g.m = (uint32_t)m;
+    g.stride = (uint32_t)((m + RJ_SAMPLES - 1) / RJ_SAMPLES);
+    g.ns = (uint32_t)((m + g.stride - 1) / g.stride);
+    g.base = base;
+    g.span = span;
+    g.lo = lo->as<uint32_t>();
+    g.count = counts->as<uint32_t>();
+    g.visited = M.visited->as<uint8_t>();
+    g.diff = diff ? diff->as<int32_t>() : nullptr;
+    {
+      ProfileScope ps("rangejoin_bounds", nl * ((a ? w : 0) + (b ? w : 0) + 9) + (diff ? m * 4 : 0));
+      with_rj_type(T, [&](auto t) { k_rj_bounds<decltype(t)::value><<<grid_for(nl, BLOCK), BLOCK, 0, r.stream>>>(g); });
+      DFGPU_HIP(hipGetLastError());
+    }
+    // ---- coverage: which right rows lie in some run
+    if (right_flags) {
+      BufPtr cover = make_buf((size_t)(m + 1) * 8);
+      scan_u32(reinterpret_cast<const uint32_t*>(diff->as<int32_t>()), m, cover->as<uint64_t>());
+      ProfileScope ps("rangejoin_cover", m * 12 + m);
+      k_rj_cover<<<grid_for(m, BLOCK), BLOCK, 0, r.stream>>>(cover->as<uint64_t>(), perm->as<uint32_t>(), (uint32_t)m, M.hit->as<uint8_t>());
+      DFGPU_HIP(hipGetLastError());
+    }
+    if (pairs_out(jt)) {
+      offsets = make_buf((size_t)(nl + 1) * 8);
+      scan_u32(counts->as<uint32_t>(), nl, offsets->as<uint64_t>());
+      n_pass = (int64_t)read_u64(offsets->as<uint64_t>() + nl);
+    }
+  }
+  return nlj_tail(left, right, jt, lout, rout, M, n_pass, [&](int64_t* pl, int64_t* pr) {
+    if (!n_pass) return;
+    const RjExpand e{offsets->as<uint64_t>(), lo->as<uint32_t>(), perm->as<uint32_t>(), (uint32_t)nl, n_pass, pl, pr};
+    const int64_t n_tiles = (n_pass + RJ_TILE - 1) / RJ_TILE;
+    ProfileScope ps("rangejoin_expand", n_pass * 20 + nl * 12);
+    k_rj_expand<<<(unsigned)std::min<int64_t>(n_tiles, (int64_t)policy().num_cus * 32), BLOCK, 0, r.stream>>>(e);
+    DFGPU_HIP(hipGetLastError());
+  });
+}
+
 }  // namespace dfgpu
 
 using namespace dfgpu;
@@ -486,6 +803,23 @@ int dfgpu_nested_loop_join(dfgpu_table_t left, dfgpu_table_t right, int join_typ
     const Table* rtb = unwrap(right);
     std::vector<int> lo(left_out_cols, left_out_cols + n_left_out), ro(right_out_cols, right_out_cols + n_right_out);
     auto o = std::make_unique<Table>(nested_loop_join(*lt, *rtb, join_type, filter, lo, ro));
+    *out = wrap(o.release());
+  });
+}
+
+int dfgpu_range_join(dfgpu_table_t left, dfgpu_table_t right, int join_type, int right_key_col, int lower_col, int lower_inclusive, int upper_col, int upper_inclusive,
+                     const int* left_out_cols, int n_left_out, const int* right_out_cols, int n_right_out, dfgpu_table_t* out) {
+  return guarded([&] {
+    require_init();
+    DFGPU_CHECK(left && right && out && n_left_out >= 0 && n_right_out >= 0 && (left_out_cols || !n_left_out) && (right_out_cols || !n_right_out), "null argument");
+    DFGPU_CHECK(join_type >= DFGPU_JOIN_INNER && join_type <= DFGPU_JOIN_RIGHT_MARK, "bad join type");
+    const Table* lt = unwrap(left);
+    const Table* rtb = unwrap(right);
+    std::vector<int> lo, ro;
+    if (n_left_out) lo.assign(left_out_cols, left_out_cols + n_left_out);
+    if (n_right_out) ro.assign(right_out_cols, right_out_cols + n_right_out);
+    auto o = std::make_unique<Table>(range_join(*lt, *rtb, join_type, right_key_col, lower_col < 0 ? -1 : lower_col, lower_inclusive != 0, upper_col < 0 ? -1 : upper_col,
+                                                upper_inclusive != 0, lo, ro));
     *out = wrap(o.release());
   });
 }

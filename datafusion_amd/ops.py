@@ -243,6 +243,30 @@ def nested_loop_join(left: DeviceTable, right: DeviceTable, join_type="Inner", j
     return DeviceTable(out)
 
 
+RANGE_JOIN_TILE = 2048   # DFGPU_RANGE_JOIN_TILE: the output pairs one workgroup of the range join's expand kernel writes
+
+
+def range_join(left: DeviceTable, right: DeviceTable, x, lower=None, upper=None, join_type="Inner", left_cols=None, right_cols=None) -> DeviceTable:
+    """dfgpu_range_join: the join `a <(=) x AND x <(=) b` of left columns a, b against ONE right column x by sorting x and searching the
+    bounds, without the pair space.  `lower` = (left column a, inclusive) or None, `upper` = (left column b, inclusive) or None; at
+    least one is needed.  Columns are given as in nested_loop_join.  The pair types come in LEFT-row-major order (ascending left row,
+    ascending x within it, equal x by ascending right row), then the unmatched right rows, then the unmatched left rows; the one-sided
+    types equal nested_loop_join's output position by position."""
+    lib = _lib.init()
+    lc = list(range(left.num_columns)) if left_cols is None else [left.index_of(c) for c in left_cols]
+    rc = list(range(right.num_columns)) if right_cols is None else [right.index_of(c) for c in right_cols]
+    if join_type in ("LeftSemi", "LeftAnti", "LeftMark"):
+        rc = []
+    if join_type in ("RightSemi", "RightAnti", "RightMark"):
+        lc = []
+    a, a_inc = (-1, False) if lower is None else (left.index_of(lower[0]), bool(lower[1]))
+    b, b_inc = (-1, False) if upper is None else (left.index_of(upper[0]), bool(upper[1]))
+    out = C.c_void_p()
+    check(lib.dfgpu_range_join(left.handle, right.handle, JOIN_TYPES[join_type], right.index_of(x), a, int(a_inc), b, int(b_inc), _ints(lc), len(lc),
+                               _ints(rc), len(rc), C.byref(out)))
+    return DeviceTable(out)
+
+
 def tail_probe_schema(right: DeviceTable, join_type, probe_cols=None):
     """the NULL-filled probe columns of the unmatched build rows of Left / Full joins (dfgpu_join_emit_unmatched's probe_fields)"""
     if join_type not in ("Left", "Full"):

@@ -19,6 +19,7 @@ per-operator GPU node):
   SortPreservingMergeExec on one GPU                 -> removed                 (one sorted partition is the merge)
 WindowAggExec stays the node it is (dfgpu_window); the rule demands order of its child, so the SortExec below keeps its meaning.
 NestedLoopJoinExec / CrossJoinExec stay the nodes they are (dfgpu_nested_loop_join); only their right child inherits the parent's need of order.
+With GpuOffloadRule(range_joins=True) a NestedLoopJoinExec over a range condition becomes a GpuRangeJoinExec (dfgpu_range_join).
 """
 from __future__ import annotations
 
@@ -493,6 +494,103 @@ class CrossJoinExec(NestedLoopJoinExec):
         return ""
 
 
+RANGE_JOIN_NO_BOUND = "a range join needs a lower or an upper bound"
+RANGE_JOIN_DICT_KEY = "a range join key that is dictionary-encoded is not supported on the GPU path"
+RANGE_JOIN_KEY_TYPE = "a range join key of a type other than Int32, Int64, Date32, UInt32, UInt64 or Float64 is not supported on the GPU path"
+RANGE_JOIN_MIXED_KEYS = "a range join over keys of different types is not supported on the GPU path"
+
+
+def _schema_field(schema, c):
+    return schema.field(schema.get_field_index(c)) if isinstance(c, str) else schema.field(c)
+
+
+class GpuRangeJoinExec(ExecutionPlan):
+    """dfgpu_range_join as a plan node: the join `a <(=) x AND x <(=) b` of the left columns a, b against the right column x by sorting x
+    and searching the bounds (no pair space).  `lower` = (left column a, inclusive) or None, `upper` = (left column b, inclusive) or None;
+    `projection` = (left columns, right columns).  Deliberately not a NestedLoopJoinExec: the pair types come in LEFT-row-major order
+    (ops.range_join), so GpuOffloadRule(range_joins=True) only puts it where that order is not observed, or for the one-sided types."""
+
+    def __init__(self, left: ExecutionPlan, right: ExecutionPlan, x, lower=None, upper=None, join_type="Inner", projection=None):
+        if join_type not in ops.JOIN_TYPES:
+            raise ValueError(f"unknown join type {join_type!r}")
+        self.left, self.right, self.x, self.lower, self.upper, self.join_type, self.projection = left, right, x, lower, upper, join_type, projection
+
+    def children(self):
+        return [self.left, self.right]
+
+    def with_new_children(self, c):
+        return GpuRangeJoinExec(c[0], c[1], self.x, self.lower, self.upper, self.join_type, self.projection)
+
+    def execute(self, partition=0):
+        l, lo = self._run_child(self.left)
+        r, ro = self._run_child(self.right)
+        lc, rc = self.projection if self.projection else (None, None)
+        try:
+            return ops.range_join(l, r, self.x, self.lower, self.upper, self.join_type, lc, rc)
+        finally:
+            for t, o in ((l, lo), (r, ro)):
+                if o:
+                    t.free()
+
+    def _label(self, child, c):
+        """name@index of a child's column, as far as the child's schema is known at plan time"""
+        try:
+            sch = plan_schema(child)
+            i = sch.get_field_index(c) if isinstance(c, str) else int(c)
+            return f"{sch.field(i).name}@{i}"
+        except Exception:  # noqa: BLE001 - no schema at plan time: what the node was given
+            return f"{c}@{None if isinstance(c, str) else c}"
+
+    def detail(self):
+        x, parts = self._label(self.right, self.x), []
+        if self.lower is not None:
+            parts.append(f"{self._label(self.left, self.lower[0])} {'<=' if self.lower[1] else '<'} {x}")
+        if self.upper is not None:
+            parts.append(f"{x} {'<=' if self.upper[1] else '<'} {self._label(self.left, self.upper[0])}")
+        return f"join_type={self.join_type}, " + (" AND ".join(parts) if parts else "no bound") + (f", projection={self.projection}" if self.projection else "")
+
+
+def range_condition(join_filter):
+    """(x, lower, upper) when the JoinFilter is one comparison (<, <=, >, >=) of a bare left column with a bare right column, or an AND of
+    two that name the same right column and give at most one lower and one upper bound on it: x = the right column's index, lower /
+    upper = (left column index, inclusive) or None.  None for every other filter."""
+    if join_filter is None:
+        return None
+    fexpr, fcols = join_filter
+    comps = [fexpr.left, fexpr.right] if isinstance(fexpr, BinaryExpr) and fexpr.op == "and" else [fexpr]
+    flipped = {"<": ">", "<=": ">=", ">": "<", ">=": "<="}
+
+    def slot(c):
+        if type(c) is not Column:
+            return None
+        k = c.index if c.index is not None else (int(c.name[1:]) if c.name[:1] == "f" and c.name[1:].isdigit() else None)
+        return k if k is not None and 0 <= k < len(fcols) else None
+
+    x, lower, upper = None, None, None
+    for c in comps:
+        if not isinstance(c, BinaryExpr) or c.op not in flipped:
+            return None
+        a, b = slot(c.left), slot(c.right)
+        if a is None or b is None or fcols[a][1] == fcols[b][1]:
+            return None
+        op = c.op
+        if fcols[a][1] == "Right":           # x op a  is  a flipped(op) x
+            a, b, op = b, a, flipped[op]
+        li, ri = int(fcols[a][0]), int(fcols[b][0])
+        if x is not None and ri != x:
+            return None
+        x = ri
+        if op in ("<", "<="):                # a <(=) x
+            if lower is not None:
+                return None
+            lower = (li, op == "<=")
+        else:                                # a >(=) x  is  x <(=) a
+            if upper is not None:
+                return None
+            upper = (li, op == ">=")
+    return x, lower, upper
+
+
 def replicated_build(node: ExecutionPlan) -> bool:
     """several ranks and the build side is a CoalescePartitionsExec (every rank holds ALL build rows: PartitionMode::CollectLeft)"""
     from .queries import _world
@@ -684,10 +782,12 @@ class GpuOffloadRule:
     joins whose parent does not need the probe-side order (an aggregate or a repartition) take the single-pass
     unordered probe where it applies (probe_mode "order_not_needed": at most one match per probe row, non-nullable
     payload; the library falls back to the general path otherwise) — the rule knows the parent because it rewrites bottom-up and fixes the child when it
-    visits the parent."""
+    visits the parent.  `range_joins=True` (one rank) turns a NestedLoopJoinExec whose filter is a range condition on one right column
+    (range_condition) over keys the device takes into a GpuRangeJoinExec — for the one-sided join types, and for the pair types where
+    the parent does not observe order, because the range join's pairs come left-row-major.  The default leaves every plan as it was."""
 
-    def __init__(self, world_size: int = 1, unordered_probe: bool = True):
-        self.world_size, self.unordered_probe = world_size, unordered_probe
+    def __init__(self, world_size: int = 1, unordered_probe: bool = True, range_joins: bool = False):
+        self.world_size, self.unordered_probe, self.range_joins = world_size, unordered_probe, range_joins
         self.declined = []    # (node, reason) of operators the rule left to the CPU
 
     def _admits(self, node) -> bool:
@@ -745,7 +845,7 @@ class GpuOffloadRule:
                 need = False                                   # these consume their input in any order
             elif isinstance(node, WindowAggExec):
                 need = True                                    # partitions and peer groups ARE the input's order, whatever the parent needs
-            elif isinstance(node, (HashJoinExec, NestedLoopJoinExec)):
+            elif isinstance(node, (HashJoinExec, NestedLoopJoinExec, GpuRangeJoinExec)):
                 need = parent_needs_order and i == 1           # only the probe side's order shows in the output
             else:
                 need = parent_needs_order                      # FilterExec / ProjectionExec / CoalesceBatchesExec keep it
@@ -782,6 +882,16 @@ class GpuOffloadRule:
         if isinstance(node, NestedLoopJoinExec) and not getattr(node, "kept_on_cpu", False) and not self._admits_pairs(node):
             node.kept_on_cpu = True
             return node
+        if self.range_joins and self.world_size == 1 and type(node) is NestedLoopJoinExec and not getattr(node, "kept_on_cpu", False):
+            cond = range_condition(node.filter)
+            if cond is not None and (node.join_type not in ("Inner", "Left", "Right", "Full") or not parent_needs_order):
+                rj = GpuRangeJoinExec(node.left, node.right, cond[0], cond[1], cond[2], node.join_type, node.projection)
+                try:
+                    taken = plan_schema(node.left) is not None and plan_schema(node.right) is not None and unsupported_reason(rj) is None
+                except Exception:  # noqa: BLE001 - children that cannot be typed at plan time: the key types are unknown, the node stays
+                    taken = False
+                if taken:
+                    return rj
         if isinstance(node, HashJoinExec) and not isinstance(node, GpuHashJoinExec):
             probe_mode = ops.PROBE_MODES["order_not_needed"] if (self.unordered_probe and not parent_needs_order and
                                                                       node.join_type in ("Inner", "RightSemi", "RightAnti")) else node.probe_mode
@@ -825,7 +935,7 @@ def _row_bound(node):
     if isinstance(node, HashJoinExec):
         (br, bb), (pr, pb) = _row_bound(node.left), _row_bound(node.right)
         return max(br, pr), bb + pb
-    if isinstance(node, NestedLoopJoinExec):
+    if isinstance(node, (NestedLoopJoinExec, GpuRangeJoinExec)):
         (br, bb), (pr, pb) = _row_bound(node.left), _row_bound(node.right)
         if node.join_type in ("LeftSemi", "LeftAnti", "LeftMark"):
             return br, bb + 1
@@ -864,7 +974,7 @@ def plan_schema(node):
         if jt == "RightMark":
             return pa.schema(rf + [pa.field("mark", pa.bool_())])
         return pa.schema(lf + rf)
-    if isinstance(node, NestedLoopJoinExec):
+    if isinstance(node, (NestedLoopJoinExec, GpuRangeJoinExec)):
         l, r = plan_schema(node.left), plan_schema(node.right)
         if l is None or r is None:
             return None
@@ -1101,6 +1211,32 @@ def unsupported_reason(node):
         bits = sum(_key_bits(inp.field(inp.get_field_index(c) if isinstance(c, str) else c).type) for c, _, _ in node.expr)
         if bits > 192:   # sort.hip: "packed sort key longer than 192 bits"
             return f"sort key of up to {bits} bits: the device packs at most 192"
+        return None
+    if isinstance(node, GpuRangeJoinExec):
+        # nlj.hip range_join: the same checks in the same order, with the same messages
+        if node.lower is None and node.upper is None:
+            return RANGE_JOIN_NO_BOUND
+        l, r = plan_schema(node.left), plan_schema(node.right)
+        if l is None or r is None:
+            return None
+        sides = [(node.right, r, node.x)] + [(node.left, l, bound[0]) for bound in (node.lower, node.upper) if bound is not None]
+        try:
+            keys = [_schema_field(sch, c) for _, sch, c in sides]
+        except (KeyError, IndexError, ValueError) as err:
+            return f"range join key column out of range: {err}"
+        taken = (pa.int32(), pa.int64(), pa.date32(), pa.uint32(), pa.uint64(), pa.float64())
+        for (child, sch, c), f in zip(sides, keys):
+            encoded = pa.types.is_dictionary(f.type)
+            if not encoded and isinstance(child, MemoryExec) and hasattr(child.table, "dictionary_size"):
+                # a device table's schema shows a dictionary-encoded column as its index type: the table itself knows
+                i = sch.get_field_index(c) if isinstance(c, str) else int(c)
+                encoded = child.table.dictionary_size(i if child.projection is None else child.table.index_of(child.projection[i])) is not None
+            if encoded:
+                return RANGE_JOIN_DICT_KEY
+            if f.type not in taken:
+                return RANGE_JOIN_KEY_TYPE
+        if any(f.type != keys[0].type for f in keys):
+            return RANGE_JOIN_MIXED_KEYS
         return None
     if isinstance(node, NestedLoopJoinExec):
         if node.filter is None:

@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define DFGPU_ABI_VERSION 19
+#define DFGPU_ABI_VERSION 20
 
 /* Arrow C Data Interface (https://arrow.apache.org/docs/format/CDataInterface.html) */
 #ifndef ARROW_C_DATA_INTERFACE
@@ -527,6 +527,35 @@ int dfgpu_join_probe_with_filter(dfgpu_join_t ht, dfgpu_table_t probe, const int
  * nlj.early_exit (0 = derived / on). */
 int dfgpu_nested_loop_join(dfgpu_table_t left, dfgpu_table_t right, int join_type, const dfgpu_join_filter* filter,
                            const int* left_out_cols, int n_left_out, const int* right_out_cols, int n_right_out, dfgpu_table_t* out);
+
+/* ABI 20 — the range join: a join whose condition is one or two range comparisons of left columns against ONE right column x,
+ * `a <(=) x AND x <(=) b`, without evaluating the pair space.  The non-NULL x are sorted once; a left row's matches are then one
+ * contiguous run of the sorted order, found by two binary searches: O((|L| + |R|) log |R| + output).
+ *   right_key_col = x;  lower_col = the left column a with a <= x (lower_inclusive != 0) or a < x, -1 = no lower bound;
+ *   upper_col = the left column b with x <= b (upper_inclusive != 0) or x < b, -1 = no upper bound.  Both -1 is an error ("a range
+ *   join needs a lower or an upper bound").
+ * A pair (l, r) matches when x[r] is not NULL, and there is no lower bound or a[l] is not NULL and a[l] <(=) x[r], and there is no
+ * upper bound or b[l] is not NULL and x[r] <(=) b[l]: exactly "the filter's value is TRUE" for the JoinFilter a <(=) x AND x <(=) b
+ * under Kleene AND.  Comparisons are the expression layer's: integers and dates by value, Float64 by the total order on its bits
+ * (-NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN).  An interval with a > b, or a == b with an exclusive end, matches nothing.
+ * x, a and b have one and the same type among Int32, Int64, Date32, UInt32, UInt64 and Float64 and are not dictionary-encoded;
+ * anything else, and a side of 2^31 rows or more (row ids in the sort are 32 bits, coverage counts Int32), "is not supported on the
+ * GPU path".
+ * All ten join types; output columns, the nullability of the NULL-extended side and the `mark` column are those of
+ * dfgpu_nested_loop_join.  Output order:
+ *   Inner / Left / Right / Full: the matching pairs in LEFT-row-major order (ascending left row; within one left row ascending x in
+ *     the key order above; equal x by ascending right row), then the unmatched right rows, ascending (Right / Full), then the
+ *     unmatched left rows, ascending (Left / Full);
+ *   LeftSemi / LeftAnti / LeftMark: left-row order;  RightSemi / RightAnti / RightMark: right-row order (for these six the output
+ *     equals dfgpu_nested_loop_join's position by position).
+ * The pair-output types count first, admit the counted output against the pool's limit and allocate exactly; an output that is not
+ * admitted fails with "Resources exhausted" before a pair is written.
+ * DFGPU_RANGE_JOIN_TILE = the output pairs one workgroup of the expand kernel writes (informative: tests place their skew and
+ * tile-edge cases by it). */
+#define DFGPU_RANGE_JOIN_TILE 2048
+int dfgpu_range_join(dfgpu_table_t left, dfgpu_table_t right, int join_type, int right_key_col, int lower_col, int lower_inclusive,
+                     int upper_col, int upper_inclusive, const int* left_out_cols, int n_left_out, const int* right_out_cols,
+                     int n_right_out, dfgpu_table_t* out);
 
 /* min / max / non-null count of an integer column and whether it is strictly ascending (the statistics
  * ArrayMap::try_new takes from the build keys, joins/array_map.rs:175-203; also the probe-key bounds the multi-GPU
