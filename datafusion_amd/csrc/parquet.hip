@@ -257,10 +257,11 @@ void walk_runs(const uint8_t* p, const uint8_t* end, int bit_width, int64_t n, F
     p = v.p;
     if (h & 1) {
       // the varint is untrusted: bound the group count by what the page can hold BEFORE multiplying (groups * bit_width
-      // would wrap for groups >= 2^58 and pass the overrun check with bytes the page does not have)
+      // would wrap for groups >= 2^58 and pass the overrun check with bytes the page does not have).  A run of width 0 (a
+      // one-entry dictionary) has no bytes at all: its groups are bounded by the values the page still owes
       const uint64_t ugroups = h >> 1;
-      DFGPU_CHECK(ugroups > 0 && ugroups <= (uint64_t)INT32_MAX && ugroups <= (uint64_t)(end - p) / (uint64_t)std::max(bit_width, 1),
-                  "parquet: bit-packed run overruns its page");
+      const uint64_t room = bit_width ? (uint64_t)(end - p) / (uint64_t)bit_width : (uint64_t)(n - done + 7) / 8;
+      DFGPU_CHECK(ugroups > 0 && ugroups <= (uint64_t)INT32_MAX && ugroups <= room, "parquet: bit-packed run overruns its page");
       const int64_t groups = (int64_t)ugroups;
       const int64_t bytes = groups * bit_width;
       DFGPU_CHECK(end - p >= bytes, "parquet: bit-packed run overruns its page");
@@ -606,6 +607,7 @@ ChunkPlan plan_chunk(const uint8_t* chunk, int64_t nbytes, const dfgpu_parquet_c
           i += cnt;
           (packed ? P.info.n_runs_bitpacked : P.info.n_runs_rle)++;
         });
+        P.info.n_plain_pages++;   // (not dictionary-encoded: counted with the PLAIN pages, like DELTA_BINARY_PACKED and BYTE_STREAM_SPLIT)
       } else {
         throw Error("parquet: BOOLEAN value encoding " + std::to_string(h.encoding) + " is not supported on the GPU scan path");
       }
@@ -1317,6 +1319,8 @@ __global__ __launch_bounds__(BLOCK) void k_pq_decode_pages(PqDevArgs a, T* __res
   __shared__ uint64_t s_min[PQ_DM];                             // miniblock: min delta of its block
   __shared__ int32_t s_bw[PQ_RB > PQ_DM ? PQ_RB : PQ_DM];      // bit width (runs: | RUN_PACKED)
   __shared__ int64_t s_pos, s_batch_end;
+  __shared__ int64_t s_m, s_wpos;                               // DELTA: next miniblock of the open block, where its width bytes lie
+  __shared__ uint64_t s_md;                                     // DELTA: the open block's min delta
   __shared__ int32_t s_n, s_err;
   __shared__ uint64_t s_wsum[BLOCK / WAVE], s_carry;
   const int p = blockIdx.x;
@@ -1467,11 +1471,14 @@ __global__ __launch_bounds__(BLOCK) void k_pq_decode_pages(PqDevArgs a, T* __res
       int64_t pos = 0;
       uint64_t block = 0, minis = 0, total = 0, first = 0;
       bool ok = dev_varint(vals, pos, vbytes, block) && dev_varint(vals, pos, vbytes, minis) && dev_varint(vals, pos, vbytes, total) && dev_varint(vals, pos, vbytes, first);
-      ok = ok && block > 0 && block % 128 == 0 && block <= (1u << 20) && minis > 0 && minis <= PQ_DM && block % minis == 0 && (block / minis) % 32 == 0 && (int64_t)total >= n;
+      ok = ok && block > 0 && block % 128 == 0 && block <= (1ull << 31) && minis > 0 && block % minis == 0 && (block / minis) % 32 == 0 && (int64_t)total >= n;
       s_hdr[0] = block;
       s_hdr[1] = minis;
       s_hdr[2] = (first >> 1) ^ (0 - (first & 1));   // zigzag
       s_pos = pos;
+      s_m = (int64_t)minis;   // (no block open: the first batch starts with a block header)
+      s_wpos = 0;
+      s_md = 0;
       s_err = ok ? PQE_NONE : PQE_DELTA;
       s_carry = s_hdr[2];
     }
@@ -1485,29 +1492,34 @@ __global__ __launch_bounds__(BLOCK) void k_pq_decode_pages(PqDevArgs a, T* __res
     int64_t done = 1;
     while (done < n && !s_err) {
       if (tid == 0) {
-        int64_t pos = s_pos, bv = 0;
+        // a batch = the next PQ_DM miniblocks, whichever blocks they lie in: a block of more miniblocks than that goes on in the next batch
+        int64_t pos = s_pos, bv = 0, m = s_m, wpos = s_wpos;
+        uint64_t md = s_md;
         int nm = 0, err = PQE_NONE;
         const int64_t left = n - done;
-        while (nm + minis <= PQ_DM && bv < left) {
-          uint64_t md;
-          if (!dev_varint(vals, pos, vbytes, md) || pos + minis > vbytes) { err = PQE_DELTA; break; }
-          md = (md >> 1) ^ (0 - (md & 1));
-          const uint8_t* widths = vals + pos;
-          pos += minis;
-          for (int64_t m = 0; m < minis && bv < left; m++) {
-            const int w = widths[m];
-            if (w > 64 || pos + per_mini * w / 8 > vbytes) { err = PQE_DELTA; break; }
-            s_start[nm] = bv;
-            s_pay[nm] = pos;
-            s_bw[nm] = w;
-            s_min[nm] = md;
-            pos += per_mini * w / 8;
-            bv += per_mini;
-            nm++;
+        while (nm < PQ_DM && bv < left) {
+          if (m == minis) {   // the next block: <min delta> <one bit width per miniblock>
+            if (!dev_varint(vals, pos, vbytes, md) || pos + minis > vbytes) { err = PQE_DELTA; break; }
+            md = (md >> 1) ^ (0 - (md & 1));
+            wpos = pos;
+            pos += minis;
+            m = 0;
           }
-          if (err) break;
+          const int w = vals[wpos + m];
+          if (w > 64 || pos + per_mini * w / 8 > vbytes) { err = PQE_DELTA; break; }
+          s_start[nm] = bv;
+          s_pay[nm] = pos;
+          s_bw[nm] = w;
+          s_min[nm] = md;
+          pos += per_mini * w / 8;
+          bv += per_mini;
+          nm++;
+          m++;
         }
         s_pos = pos;
+        s_m = m;
+        s_wpos = wpos;
+        s_md = md;
         s_n = nm;
         s_batch_end = bv < left ? bv : left;   // values of this batch
         s_err = err;

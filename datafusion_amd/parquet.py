@@ -5,8 +5,11 @@ Host side of the GPU scan node a DataFusion shim would put in place of `DataSour
 its byte range -> `dfgpu_parquet_decode_chunk` (include/dfgpu.h; page headers, decompression and run headers on the host,
 value decoding on the device) -> row groups assembled with dfgpu_table_hstack / dfgpu_table_concat.  The footer is read
 with pyarrow here (the shim has it from the `parquet` crate's `ParquetMetaData`); no value byte is decoded on the CPU.
-Unsupported chunks (nested columns, DELTA / BYTE_STREAM_SPLIT encodings, strings outside a dictionary, other codecs) raise
-DfgpuError: the rule keeps the CPU scan for such files.
+Read: flat columns of INT32 / INT64 / DOUBLE / FIXED_LEN_BYTE_ARRAY (decimals of 1..16 bytes) / BOOLEAN / BYTE_ARRAY in data pages v1 and
+v2 (with the per-page is_compressed flag), PLAIN, dictionary (index widths 0..32), DELTA_BINARY_PACKED, BYTE_STREAM_SPLIT and RLE Boolean
+values, UNCOMPRESSED / SNAPPY / ZSTD; a string column arrives dictionary-encoded when all its pages are, as Utf8 when any is PLAIN.
+Unsupported chunks (nested columns, INT96 / FLOAT, DELTA_LENGTH_BYTE_ARRAY / DELTA_BYTE_ARRAY strings, other codecs) raise DfgpuError:
+the rule keeps the CPU scan for such files.
 """
 from __future__ import annotations
 

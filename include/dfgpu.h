@@ -902,8 +902,11 @@ typedef struct dfgpu_parquet_column {
                                   * dictionary-encoded) -> Int32 indices of a dictionary-encoded string column (ascending dictionary) */
   const char* name;
 } dfgpu_parquet_column;
-/* Supported: data pages v1 / v2, PLAIN / PLAIN_DICTIONARY / RLE_DICTIONARY values, RLE definition levels, UNCOMPRESSED /
- * SNAPPY / ZSTD (libzstd.so.1 on the host).  Anything else returns an error and the caller keeps the CPU scan.
+/* Supported: data pages v1 / v2 (v2 with its per-page is_compressed flag), PLAIN / PLAIN_DICTIONARY / RLE_DICTIONARY values
+ * (index bit widths 0..32), DELTA_BINARY_PACKED (INT32 / INT64), BYTE_STREAM_SPLIT (INT32 / INT64 / DOUBLE /
+ * FIXED_LEN_BYTE_ARRAY), BOOLEAN columns (PLAIN bits / RLE runs), BYTE_ARRAY with PLAIN pages when read as Utf8 (field.type
+ * DFGPU_UTF8), RLE definition levels, UNCOMPRESSED / SNAPPY / ZSTD (libzstd.so.1 on the host).  Anything else returns an
+ * error and the caller keeps the CPU scan.
  * `out` = a one-column device table of num_values rows. */
 int dfgpu_parquet_decode_chunk(const uint8_t* chunk, int64_t chunk_bytes, const dfgpu_parquet_column* column, dfgpu_table_t* out);
 /* the host half alone (page headers, decompression, levels, run headers): needs no GPU and no dfgpu_init */
