@@ -1078,7 +1078,132 @@ __global__ __launch_bounds__(BLOCK) void k_var_merge(VarSet s, int64_t G) {
     }
 }
 
+// ------------------------------------------------------------------- COUNT(DISTINCT) / SUM(DISTINCT)
+// A DISTINCT aggregate keeps a set of (group number, value bits) that lives as long as the node: an entry store — gid, lo and, for
+// Decimal128, hi, one element per pair, appended — and an open-addressing table of 32-bit slots over it (a power of two of them, at
+// most half full, linear probing from fmix64 over the pair).  A slot holds 0 (empty), entry + 1, or DS_ROW | row: a row of the batch
+// being inserted.
+//
+// Why the insert is race-free.  A lane that meets an empty slot claims it with ONE 32-bit CAS of its own row number.  Slots are
+// only ever written by that CAS while rows are inserted, so a slot that is not empty never changes again in the launch, and two
+// lanes holding the same pair walk the same slots: the one whose CAS comes second — in the same wave, in another wave, on another
+// XCD — is handed the winner's row number by the CAS itself and finds its own pair behind it.  What it compares with is the batch's
+// argument column and the interned keys (a row slot) or an entry an EARLIER launch stored (an entry slot): nothing a lane reads was
+// written by another lane of this launch except the slot word, which is only touched by agent-scope atomics.  The winner appends its
+// pair to the entry store and notes its slot there; no lane of this launch reads that entry.  k_distinct_publish, the next launch, turns
+// the row slots into entry slots, so the batch can go.  A pair is therefore stored exactly once, whatever races.
+constexpr uint32_t DS_ROW = 0x80000000u;
+struct DistinctDev {
+  uint32_t* slots;
+  uint64_t mask;             // slots - 1
+  uint32_t* e_gid;
+  uint32_t* e_slot;          // the slot that holds the entry (what publish rewrites, what a regrown table sets anew)
+  unsigned long long* e_lo;
+  unsigned long long* e_hi;  // Decimal128 only, else null
+  uint32_t* count;           // entries stored
+};
+__device__ __forceinline__ uint64_t distinct_start(uint32_t gid, uint64_t lo, uint64_t hi, bool wide) {
+  uint64_t h = fmix64(lo ^ fmix64((uint64_t)gid ^ SEED_AGG));
+  if (wide) h = fmix64(h ^ hi);
+  return h;
+}
+// the argument of row i as the set sees it: false = NULL (by validity, or a dictionary code whose value is NULL).  `remap`: code ->
+// the first code of the same string (an imported dictionary may repeat a value), ~0 = the value is NULL
+__device__ __forceinline__ bool distinct_value(const AccDesc& d, const uint32_t* remap, uint32_t remap_n, bool wide, int64_t i, uint64_t& lo, uint64_t& hi) {
+  if (d.valid && !bit_at(d.valid, i)) return false;
+  load_value(d, i, lo, hi);
+  if (!wide) hi = 0;
+  if (remap) {
+    if (lo >= remap_n) return false;
+    lo = remap[lo];
+    if (lo == 0xFFFFFFFFull) return false;
+  }
+  return true;
+}
+__global__ __launch_bounds__(BLOCK) void k_distinct_insert(InternCtx c, const uint32_t* __restrict__ slot_gid, int has_groups, int64_t row_offset, int64_t n, AccDesc d,
+                                                          const uint32_t* __restrict__ remap, uint32_t remap_n, DistinctDev s) {
+  const bool wide = s.e_hi != nullptr;
+  for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
+    uint64_t lo, hi;
+    if (!distinct_value(d, remap, remap_n, wide, i, lo, hi)) continue;
+    const uint32_t gid = has_groups ? lookup_gid(c, slot_gid, row_offset + i) : 0u;
+    uint64_t p = distinct_start(gid, lo, hi, wide) & s.mask;
+    for (;;) {
+      uint32_t cur = __hip_atomic_load(&s.slots[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (cur == 0u) {
+        cur = atomicCAS(&s.slots[p], 0u, DS_ROW | (uint32_t)i);
+        if (cur == 0u) {   // this row stands for the pair
+          const uint32_t j = atomicAdd(s.count, 1u);
+          s.e_gid[j] = gid;
+          s.e_slot[j] = (uint32_t)p;
+          s.e_lo[j] = lo;
+          if (wide) s.e_hi[j] = hi;
+          break;
+        }
+      }
+      bool same;
+      if (cur & DS_ROW) {
+        const int64_t r = (int64_t)(cur & ~DS_ROW);
+        uint64_t rlo, rhi;
+        same = r == i || (distinct_value(d, remap, remap_n, wide, r, rlo, rhi) && rlo == lo && rhi == hi &&
+                          (has_groups ? lookup_gid(c, slot_gid, row_offset + r) : 0u) == gid);
+      } else {
+        const uint32_t j = cur - 1u;
+        same = s.e_lo[j] == lo && (!wide || s.e_hi[j] == hi) && s.e_gid[j] == gid;
+      }
+      if (same) break;
+      p = (p + 1) & s.mask;
+    }
+  }
+}
+// the slots the batch's rows claimed now name the entries those rows appended
+__global__ __launch_bounds__(BLOCK) void k_distinct_publish(DistinctDev s, uint32_t first) {
+  const uint32_t end = *s.count;
+  for (uint32_t j = first + blockIdx.x * BLOCK + threadIdx.x; j < end; j += gridDim.x * BLOCK) s.slots[s.e_slot[j]] = j + 1u;
+}
+// a larger (zeroed) table takes the entries again: they are all different, so a claimed slot is simply passed
+__global__ __launch_bounds__(BLOCK) void k_distinct_grow(DistinctDev s, uint32_t entries) {
+  const bool wide = s.e_hi != nullptr;
+  for (uint32_t j = blockIdx.x * BLOCK + threadIdx.x; j < entries; j += gridDim.x * BLOCK) {
+    uint64_t p = distinct_start(s.e_gid[j], s.e_lo[j], wide ? s.e_hi[j] : 0ull, wide) & s.mask;
+    while (atomicCAS(&s.slots[p], 0u, j + 1u) != 0u) p = (p + 1) & s.mask;
+    s.e_slot[j] = (uint32_t)p;
+  }
+}
+// emit: every entry adds 1 (COUNT) or its value (SUM: kind = ACC_SUM_I64 / ACC_SUM_I128, wrapping) to its group's cell.  Integer
+// sums commute: the result does not depend on the order of the entries
+__global__ __launch_bounds__(BLOCK) void k_distinct_reduce(DistinctDev s, uint32_t entries, int kind, unsigned long long* __restrict__ acc_lo,
+                                                          unsigned long long* __restrict__ acc_hi, uint32_t* __restrict__ seen) {
+  for (uint32_t j = blockIdx.x * BLOCK + threadIdx.x; j < entries; j += gridDim.x * BLOCK) {
+    const uint32_t gid = s.e_gid[j];
+    accumulate_cell(kind, acc_lo + gid, acc_hi ? acc_hi + gid : nullptr, s.e_lo[j], s.e_hi ? s.e_hi[j] : 0ull);
+    if (seen) seen[gid] = 1u;
+  }
+}
+
 // ------------------------------------------------------------------------------- host
+// the set of one DISTINCT argument (shared by the aggregates of a node over the same argument expression and filter)
+struct DistinctSet {
+  bool typed = false;
+  dfgpu_field type{};          // the argument's column type (a string argument: the type of its codes)
+  int val = 0;                 // ValKind the values are loaded with
+  bool wide = false;           // Decimal128: 128 value bits
+  bool strings = false;        // the values are dictionary codes
+  std::shared_ptr<const DictValues> dict;
+  BufPtr remap;                // strings: code -> first code of the same string
+  uint32_t remap_n = 0;
+  BufPtr slots;
+  int64_t n_slots = 0;
+  BufPtr e_gid, e_slot, e_lo, e_hi;
+  int64_t cap = 0;             // elements of the entry store
+  int64_t entries = 0;         // as read back after the last update
+  BufPtr count;
+  std::shared_ptr<PinnedBuf> count_host;
+  DistinctDev dev() const {
+    return DistinctDev{slots->as<uint32_t>(), (uint64_t)n_slots - 1, e_gid->as<uint32_t>(), e_slot->as<uint32_t>(), e_lo->as<unsigned long long>(),
+                       wide ? e_hi->as<unsigned long long>() : nullptr, count->as<uint32_t>()};
+  }
+};
 struct AggState {
   int func;               // dfgpu_agg_func
   bool has_arg;
@@ -1100,6 +1225,7 @@ struct AggState {
   // accumulator storage
   BufPtr lo, hi, seen;    // primary accumulator (sum / min / max / count)
   BufPtr cnt;             // AVG: row count
+  std::shared_ptr<DistinctSet> dset;   // COUNT / SUM(DISTINCT): the set; lo / hi / seen are filled from it when the node emits
   // SUM over Decimal128 written by the ordered-input runs node as the first update: {lo, hi} side by side, 16 bytes per group —
   // the Decimal128 column itself, which emit hands out as it is (the lo / hi arrays would cost a 2 x 8 -> 16 byte pass over
   // every group: 1.0 of the 7.2 ms of GROUP BY l_orderkey at SF100).  lo / hi are stale while this is set; the next update
@@ -1207,6 +1333,137 @@ static BufPtr grown(const BufPtr& old, int64_t old_n, int64_t new_n, unsigned lo
   return b;
 }
 
+// ---- COUNT / SUM(DISTINCT): the host side of the set (kernels: beside the VAR block)
+static bool is_distinct(int func) { return func == DFGPU_AGG_COUNT_DISTINCT || func == DFGPU_AGG_SUM_DISTINCT; }
+static const char* distinct_name(int func) { return func == DFGPU_AGG_COUNT_DISTINCT ? "COUNT(DISTINCT)" : "SUM(DISTINCT)"; }
+// the argument types of include/dfgpu.h; a string argument is a Utf8 column (interned below) or a dictionary-encoded one
+static void distinct_check_type(const AggState& a, const Column& v) {
+  const std::string what = distinct_name(a.func);
+  const int t = v.field.type;
+  DFGPU_CHECK(t != DFGPU_BOOL, what + " over Boolean is not supported on the GPU path");
+  const bool strings = t == DFGPU_UTF8 || v.dict;
+  const bool summable = t == DFGPU_INT32 || t == DFGPU_INT64 || t == DFGPU_UINT8 || t == DFGPU_UINT32 || t == DFGPU_UINT64 || t == DFGPU_DECIMAL128;
+  if (a.func == DFGPU_AGG_SUM_DISTINCT) {
+    DFGPU_CHECK(!strings, what + " over Utf8 is not supported on the GPU path");
+    DFGPU_CHECK(summable, what + " over " + type_name(v.field) + " is not supported on the GPU path");
+  } else {
+    DFGPU_CHECK(strings || summable || t == DFGPU_DATE32 || t == DFGPU_FLOAT64, what + " over " + type_name(v.field) + " is not supported on the GPU path");
+  }
+}
+static int distinct_val_kind(int type) {
+  switch (type) {
+    case DFGPU_INT64: return VAL_I64;
+    case DFGPU_UINT8: return VAL_U8;
+    case DFGPU_UINT32: return VAL_U32;
+    case DFGPU_UINT64: return VAL_U64;
+    case DFGPU_FLOAT64: return VAL_F64;      // the bits: +0.0 and -0.0, two NaN payloads are different values (the reference's Hashable<T>)
+    case DFGPU_DECIMAL128: return VAL_I128;
+    default: return VAL_I32;                 // Int32, Date32
+  }
+}
+// binds the set to its argument on the first update and holds later ones to it; `v` leaves as the column the kernels read (a Utf8
+// argument interned, the way Utf8 group keys are).  A set that holds nothing yet — no update so far, or only rows without a value —
+// is bound anew: like the group keys' check, the dictionary only has to stay while something was counted by its codes
+static void distinct_bind(DistinctSet& ds, Column& v, const std::string& name) {
+  if (v.field.type == DFGPU_UTF8 && !v.dict) v = dictionary_encode(v, true);
+  if (ds.typed && ds.entries == 0) {
+    const BufPtr count = ds.count;   // (zero: nothing was stored)
+    const std::shared_ptr<PinnedBuf> count_host = ds.count_host;
+    ds = DistinctSet{};
+    ds.count = count;
+    ds.count_host = count_host;
+  }
+  if (ds.typed) {
+    DFGPU_CHECK(ds.type.type == v.field.type && ds.strings == (v.dict != nullptr), "aggregate " + name + ": the argument's type changed between updates");
+    DFGPU_CHECK(same_dictionary(ds.dict, v.dict),
+                "aggregate " + name + ": the dictionary changed between updates (unify the inputs' dictionaries first, e.g. dfgpu_table_concat)");
+    return;
+  }
+  ds.typed = true;
+  ds.type = v.field;
+  ds.val = distinct_val_kind(v.field.type);
+  ds.wide = v.field.type == DFGPU_DECIMAL128;
+  ds.strings = v.dict != nullptr;
+  ds.dict = v.dict;
+  if (ds.strings) {
+    // an imported Arrow dictionary may repeat a value: every code stands for the first code of its string, a NULL value for NULL
+    const DictValues& dv = *v.dict;
+    std::vector<uint32_t> map(dv.values.size() ? dv.values.size() : 1, 0xFFFFFFFFu);
+    std::map<std::string, uint32_t> first;
+    for (size_t i = 0; i < dv.values.size(); i++) {
+      if (i < dv.valid.size() && !dv.valid[i]) continue;
+      map[i] = first.emplace(dv.values[i], (uint32_t)i).first->second;
+    }
+    ds.remap_n = (uint32_t)dv.values.size();
+    ds.remap = make_buf(map.size() * 4);
+    h2d_async(ds.remap->ptr, map.data(), map.size() * 4);
+    DFGPU_HIP(hipStreamSynchronize(rt().stream));   // `map` is a host temporary; a dictionary is small and this happens once per binding
+  }
+}
+// before an update of n rows: room for entries + n entries, and at least twice as many slots (agg.distinct_slots: a test's way to
+// start small).  The bytes are admitted by the pool first: a size it cannot take fails with its message
+static void distinct_reserve(DistinctSet& ds, int64_t n) {
+  Runtime& r = rt();
+  const int64_t need = ds.entries + n;
+  DFGPU_CHECK(need < (int64_t)DS_ROW - 1, "a DISTINCT aggregate's set addresses its entries with 31 bits: " + std::to_string(need) + " are not supported on the GPU path");
+  if (!ds.count) {
+    ds.count = make_zero_buf(16);
+    ds.count_host = std::make_shared<PinnedBuf>(16);
+  }
+  const int ebytes = 4 + 4 + 8 + (ds.wide ? 8 : 0);
+  if (need > ds.cap) {
+    const int64_t cap = std::max<int64_t>(need, 2 * ds.cap);
+    pool_admit(cap * ebytes);
+    auto regrow = [&](BufPtr& b, int elem) {
+      BufPtr nb = make_buf((size_t)cap * elem);
+      if (b && ds.entries) DFGPU_HIP(hipMemcpyAsync(nb->ptr, b->ptr, (size_t)ds.entries * elem, hipMemcpyDeviceToDevice, r.stream));
+      b = nb;
+    };
+    regrow(ds.e_gid, 4);
+    regrow(ds.e_slot, 4);
+    regrow(ds.e_lo, 8);
+    if (ds.wide) regrow(ds.e_hi, 8);
+    ds.cap = cap;
+  }
+  int64_t have = ds.n_slots;
+  if (have == 0) {
+    const int64_t first = option_int("agg.distinct_slots", 0);
+    for (have = first > 0 ? 2 : 0; have > 0 && have < first; have *= 2) {}
+  }
+  int64_t want = have;
+  if (want < 2 * need || want == 0) {
+    for (want = 64; want < 2 * need; want *= 2) {}
+    want = std::max(want, 2 * have);
+  }
+  if (want == ds.n_slots) return;
+  pool_admit(want * 4);
+  ds.slots = make_zero_buf((size_t)want * 4);
+  ds.n_slots = want;
+  if (ds.entries > 0) {
+    ProfileScope ps("agg_distinct_grow", ds.entries * (ebytes + 4));
+    k_distinct_grow<<<grid_for(ds.entries, BLOCK), BLOCK, 0, r.stream>>>(ds.dev(), (uint32_t)ds.entries);
+    DFGPU_HIP(hipGetLastError());
+  }
+}
+// the batch's pairs into the set; the entry count follows the kernels to the host and is read after the update's final wait
+static void distinct_insert(DistinctSet& ds, const InternCtx& ictx, const uint32_t* slot_gid, bool has_groups, int64_t row_offset, int64_t n, const Column& v) {
+  Runtime& r = rt();
+  AccDesc d{};
+  d.values = v.ptr();
+  d.valid = v.valid_words();
+  d.val = ds.val;
+  {
+    // (two launches: the claims, then the claimed slots renamed from rows to entries)
+    ProfileScope ps("agg_distinct_insert", n * (type_width(ds.type.type) + 4));
+    k_distinct_insert<<<grid_for(n, BLOCK), BLOCK, 0, r.stream>>>(ictx, slot_gid, has_groups ? 1 : 0, row_offset, n, d, ds.remap ? ds.remap->as<uint32_t>() : nullptr, ds.remap_n,
+                                                                 ds.dev());
+    DFGPU_HIP(hipGetLastError());
+    k_distinct_publish<<<std::min(grid_for(n, BLOCK), 1024), BLOCK, 0, r.stream>>>(ds.dev(), (uint32_t)ds.entries);
+    DFGPU_HIP(hipGetLastError());
+  }
+  DFGPU_HIP(hipMemcpyAsync(ds.count_host->ptr, ds.count->ptr, 4, hipMemcpyDeviceToHost, r.stream));
+}
+
 // what one aggregate accumulates, given its input column type
 struct AccPlan {
   int kind, val;
@@ -1226,6 +1483,11 @@ static AccPlan plan_for(int func, const dfgpu_field& t, bool merging_counts) {
         case DFGPU_INT64: return {ACC_SUM_F64, VAL_I64_TO_F64, true};
       }
       throw Error("VAR/STDDEV over " + type_name(t) + " is not supported on the GPU path (the planner casts the argument to Float64)");
+    // DISTINCT: the cells are filled from the set when the node emits (k_distinct_reduce): a count per entry, or SUM's own plan
+    case DFGPU_AGG_COUNT_DISTINCT: return {ACC_COUNT, VAL_I64, false};
+    case DFGPU_AGG_SUM_DISTINCT:
+      DFGPU_CHECK(t.type != DFGPU_FLOAT64, "SUM(DISTINCT) over Float64 is not supported on the GPU path");
+      return plan_for(DFGPU_AGG_SUM, t, false);
     case DFGPU_AGG_COUNT:
       // Final modes merge partial counts by summing them (count.rs merge_batch)
       if (merging_counts) return {ACC_SUM_I64, t.type == DFGPU_UINT64 ? VAL_U64 : VAL_I64, false};
@@ -2009,11 +2271,12 @@ static std::vector<AccPlan> grow_accumulators(Aggregate& A, int64_t G0, int64_t 
     };
     for (AggState& a : A.aggs) {
       AccPlan p = plan_for(a.func, a.in_type, final_mode);
+      plans.push_back(p);
+      if (is_distinct(a.func)) continue;   // (its cells exist from emit on)
       fresh(a.lo, acc_identity(p.kind), 8);
       if (p.needs_hi) fresh(a.hi, 0ull, 8);
       fresh(a.seen, 0ull, 4);
       if (a.func == DFGPU_AGG_AVG || is_variance(a.func)) fresh(a.cnt, 0ull, 8);
-      plans.push_back(p);
     }
     if (m) {
       k_fill_many<<<dim3((unsigned)grid_for(G1, BLOCK), (unsigned)m), BLOCK, 0, rt().stream>>>(fm, G1);
@@ -2023,11 +2286,12 @@ static std::vector<AccPlan> grow_accumulators(Aggregate& A, int64_t G0, int64_t 
   }
   for (AggState& a : A.aggs) {
     AccPlan p = plan_for(a.func, a.in_type, final_mode);
+    plans.push_back(p);
+    if (is_distinct(a.func)) continue;
     a.lo = grown(a.lo, G0, G1, acc_identity(p.kind), 8, init);
     if (p.needs_hi) a.hi = grown(a.hi, G0, G1, 0ull, 8, init);
     a.seen = grown(a.seen, G0, G1, 0, 4, init);
     if (a.func == DFGPU_AGG_AVG || is_variance(a.func)) a.cnt = grown(a.cnt, G0, G1, 0ull, 8, init);
-    plans.push_back(p);
   }
   return plans;
 }
@@ -4434,6 +4698,11 @@ static bool agg_update_fused(Aggregate& A, const Table& in, const dfgpu_expr* pr
       return false;
     }
   for (const AggState& a : A.aggs)
+    if (is_distinct(a.func)) {
+      why = "DISTINCT aggregates keep a set per group";
+      return false;
+    }
+  for (const AggState& a : A.aggs)
     if (a.has_arg && (a.func == DFGPU_AGG_MIN || a.func == DFGPU_AGG_MAX)) {
       dfgpu_expr e{a.nodes.data(), (int)a.nodes.size(), a.root};
       if (wide_minmax(a.func, expr_type(e, in))) {
@@ -4694,6 +4963,21 @@ static void agg_update_unfused(Aggregate& A, const Table& in) {
       a.typed = true;
     }
     if (inputs[k].has_v && wide_minmax(a.func, inputs[k].v.field)) wide_minmax_values_fit(inputs[k].v, a.name);
+    if (is_distinct(a.func)) distinct_check_type(a, inputs[k].v);
+  }
+  // DISTINCT: every set is bound to its argument (a Utf8 one interned) and given room for this batch; aggregates that share a set
+  // share the work.  Done before anything changes the node: a refusal leaves it as it was
+  std::vector<std::pair<DistinctSet*, size_t>> dsets;   // (set, the first aggregate that holds it)
+  for (size_t k = 0; k < A.aggs.size(); k++) {
+    AggState& a = A.aggs[k];
+    if (!is_distinct(a.func)) continue;
+    bool listed = false;
+    for (auto& d : dsets) listed |= d.first == a.dset.get();
+    if (listed) continue;
+    if (n == 0) continue;   // (an update over no rows binds nothing: a Utf8 argument would leave an empty dictionary behind)
+    distinct_bind(*a.dset, inputs[k].v, a.name);
+    distinct_reserve(*a.dset, n);
+    dsets.emplace_back(a.dset.get(), k);
   }
 
   // ---- intern (GroupValues::intern)
@@ -4716,6 +5000,7 @@ static void agg_update_unfused(Aggregate& A, const Table& in) {
   for (size_t k = 0; k < A.aggs.size(); k++) {
     AggState& a = A.aggs[k];
     const AccPlan& p = plans[k];
+    if (is_distinct(a.func)) continue;   // (no cell per group: the pass after the accumulation below)
     if (is_variance(a.func)) {
       // pass 1 counts and sums this batch's values per group into fresh cells; pass 2 and the merge follow the accumulation below
       if (n == 0) continue;
@@ -4794,7 +5079,7 @@ static void agg_update_unfused(Aggregate& A, const Table& in) {
       accs.a[accs.n++] = c;
     }
   }
-  if (n == 0 || accs.n == 0) {
+  if (n == 0 || (accs.n == 0 && dsets.empty())) {
     A.ngroups = G1;
     return;
   }
@@ -4802,9 +5087,11 @@ static void agg_update_unfused(Aggregate& A, const Table& in) {
   int64_t bytes = 0;
   for (int k = 0; k < accs.n; k++)
     if (accs.a[k].values) bytes += n * 8;
-  const int per_rep = accs.n * (int)std::min<int64_t>(G1, LDS_CELLS + 1);
+  const int per_rep = std::max(1, accs.n) * (int)std::min<int64_t>(G1, LDS_CELLS + 1);
   const uint32_t* sg = IR.slot_gid ? IR.slot_gid->as<uint32_t>() : nullptr;
-  if (G1 * accs.n <= LDS_CELLS) {
+  if (accs.n == 0) {
+    // (DISTINCT aggregates only: nothing has a cell per group)
+  } else if (G1 * accs.n <= LDS_CELLS) {
     int nrep = std::max(1, std::min(64, LDS_CELLS / per_rep));
     // power of two so that consecutive lanes spread over the replicas
     int p2 = 1;
@@ -4846,8 +5133,11 @@ static void agg_update_unfused(Aggregate& A, const Table& in) {
     k_var_merge<<<grid_for(G1, BLOCK), BLOCK, 0, r.stream>>>(vars, G1);
     DFGPU_HIP(hipGetLastError());
   }
+  // COUNT / SUM(DISTINCT): this batch's (group, value) pairs into the sets, after the ordinary accumulators have run
+  for (auto& d : dsets) distinct_insert(*d.first, ictx, sg, ngk > 0, G0, n, inputs[d.second].v);
   A.ngroups = G1;
   DFGPU_HIP(hipStreamSynchronize(r.stream));  // temporaries (evaluated columns, tables) are released on return
+  for (auto& d : dsets) d.first->entries = *reinterpret_cast<volatile uint32_t*>(d.first->count_host->ptr);   // (the count rode on that wait)
 }
 
 // aggregate_batch_inner over a whole table, optionally under a FilterExec predicate fused in front
@@ -5009,10 +5299,24 @@ static Table agg_emit(Aggregate& A) {
     }
     const bool fin = A.final_mode();
     AccPlan p = plan_for(a.func, a.in_type, fin);
+    if (is_distinct(a.func)) {
+      // the group cells of a DISTINCT aggregate are made here, from nothing, every time the node emits: one pass over the set's entries
+      a.lo = make_zero_buf((size_t)(G ? G : 1) * 8);
+      a.hi = p.needs_hi ? make_zero_buf((size_t)(G ? G : 1) * 8) : nullptr;
+      a.seen = make_zero_buf((size_t)(G ? G : 1) * 4);
+      const DistinctSet& ds = *a.dset;
+      if (ds.entries > 0) {
+        ProfileScope ps("agg_distinct_reduce", ds.entries * (4 + (a.func == DFGPU_AGG_COUNT_DISTINCT ? 0 : ds.wide ? 16 : 8) + (p.needs_hi ? 16 : 8)));
+        k_distinct_reduce<<<grid_for(ds.entries, BLOCK), BLOCK, 0, r.stream>>>(ds.dev(), (uint32_t)ds.entries, p.kind, a.lo->as<unsigned long long>(),
+                                                                             a.hi ? a.hi->as<unsigned long long>() : nullptr, a.seen->as<uint32_t>());
+        DFGPU_HIP(hipGetLastError());
+      }
+    }
     // value type of the primary accumulator when emitted
     auto value_field = [&]() -> dfgpu_field {
       switch (a.func) {
-        case DFGPU_AGG_COUNT: return fld(DFGPU_INT64);
+        case DFGPU_AGG_COUNT: case DFGPU_AGG_COUNT_DISTINCT: return fld(DFGPU_INT64);
+        case DFGPU_AGG_SUM_DISTINCT: return sum_type(a.in_type);
         case DFGPU_AGG_SUM: return fin ? a.in_type : sum_type(a.in_type);
         case DFGPU_AGG_AVG: return fin ? a.in_type : avg_sum_type(a.in_type);
         default: return a.in_type;
@@ -5067,7 +5371,7 @@ static Table agg_emit(Aggregate& A) {
       }
       continue;
     }
-    bool nullable = a.func != DFGPU_AGG_COUNT && !a.seen_all;
+    bool nullable = a.func != DFGPU_AGG_COUNT && a.func != DFGPU_AGG_COUNT_DISTINCT && !a.seen_all;
     // partial state field names: format_state_name (expr/src/utils.rs:1416) — `name[sum]` (sum.rs:293-299), `name[count]`
     // (count.rs:317-323), `name[value]` for MIN / MAX (the default AggregateUDFImpl::state_fields, expr/src/udaf.rs:579-585)
     // BIT_* / BOOL_*: one state column of the argument's type, named like the aggregate
@@ -5160,8 +5464,16 @@ int dfgpu_agg_create(int mode, const dfgpu_expr* group_by, const char* const* gr
     for (int k = 0; k < n_aggs; k++) {
       AggState a;
       a.func = aggs[k].func;
-      DFGPU_CHECK(a.func >= DFGPU_AGG_SUM && a.func <= DFGPU_AGG_BOOL_OR, "unsupported aggregate function");
+      DFGPU_CHECK(a.func >= DFGPU_AGG_SUM && a.func <= DFGPU_AGG_SUM_DISTINCT, "unsupported aggregate function");
       a.has_arg = aggs[k].has_arg != 0;
+      if (is_distinct(a.func)) {
+        // the reference's partial state of a DISTINCT aggregate is a List column, which has no device form: single-stage modes only
+        static const char* const MODE_NAMES[] = {"Partial", "Final", "FinalPartitioned", "Single", "SinglePartitioned", "PartialReduce"};
+        const std::string who = std::string(distinct_name(a.func)) + " (aggregate " + (aggs[k].name ? aggs[k].name : "") + ")";
+        DFGPU_CHECK(mode == DFGPU_AGG_SINGLE || mode == DFGPU_AGG_SINGLE_PARTITIONED,
+                    who + " is not supported in mode " + MODE_NAMES[mode] + " on the GPU path: its partial state is a List column");
+        DFGPU_CHECK(a.has_arg && aggs[k].arg.nodes && aggs[k].arg.n_nodes >= 1, who + " needs an argument");
+      }
       DFGPU_CHECK(a.has_arg || a.func == DFGPU_AGG_COUNT, "only COUNT may omit its argument");
       if (a.has_arg && aggs[k].arg.nodes) {
         a.nodes.assign(aggs[k].arg.nodes, aggs[k].arg.nodes + aggs[k].arg.n_nodes);
@@ -5184,6 +5496,21 @@ int dfgpu_agg_create(int mode, const dfgpu_expr* group_by, const char* const* gr
           a.filter_pool.assign(f.string_pool, pool);
         }
       }
+      if (is_distinct(a.func)) {
+        // two aggregates over the same argument expression and filter share one set
+        auto same_nodes = [](const std::vector<dfgpu_expr_node>& x, const std::vector<dfgpu_expr_node>& y) {
+          return x.size() == y.size() && (x.empty() || std::memcmp(x.data(), y.data(), x.size() * sizeof(dfgpu_expr_node)) == 0);
+        };
+        bool literal_strings = false;   // (an argument's string literals live in a pool that is not compared here)
+        for (const dfgpu_expr_node& nd : a.nodes) literal_strings |= nd.op == DFGPU_EXPR_LITERAL && nd.field.type == DFGPU_UTF8;
+        for (const AggState& b : A->aggs)
+          if (!literal_strings && is_distinct(b.func) && b.root == a.root && same_nodes(b.nodes, a.nodes) && b.has_filter == a.has_filter &&
+              b.filter_root == a.filter_root && same_nodes(b.filter_nodes, a.filter_nodes) && b.filter_pool == a.filter_pool) {
+            a.dset = b.dset;
+            break;
+          }
+        if (!a.dset) a.dset = std::make_shared<DistinctSet>();
+      }
       A->aggs.push_back(std::move(a));
     }
     *out = reinterpret_cast<dfgpu_agg_t>(A.release());
@@ -5202,6 +5529,9 @@ int dfgpu_agg_create_grouping_sets(int mode, const dfgpu_expr* group_by, const d
     DFGPU_CHECK(mode == DFGPU_AGG_PARTIAL || mode == DFGPU_AGG_SINGLE || mode == DFGPU_AGG_SINGLE_PARTITIONED,
                 "grouping sets: Final modes group by the partial state's key columns (the n_group keys and __grouping_id): use dfgpu_agg_create");
     DFGPU_CHECK(group_by && null_by && groups && n_group >= 1 && n_group <= 63 && n_sets >= 1 && out, "grouping sets: bad argument");
+    for (int k = 0; k < n_aggs; k++)
+      DFGPU_CHECK(!is_distinct(aggs[k].func), std::string("grouping sets: ") + distinct_name(aggs[k].func) + " (aggregate " + (aggs[k].name ? aggs[k].name : "") +
+                                                  ") is not supported on the GPU path");
     auto top = std::make_unique<Aggregate>();
     top->mode = mode;
     // Aggregate::grouping_id_type: UInt8 / UInt16 / UInt32 / UInt64 by the number of grouping columns.  The device has no UInt16

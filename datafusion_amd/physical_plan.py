@@ -601,14 +601,24 @@ def replicated_build(node: ExecutionPlan) -> bool:
     return isinstance(node, CoalescePartitionsExec)
 
 
-def _partial_below(node: ExecutionPlan):
-    """the Partial aggregate feeding a Final one, through the exchange / bookkeeping nodes between them"""
+def _partial_below(node: ExecutionPlan, through=None):
+    """the Partial aggregate feeding a Final one, through the exchange / bookkeeping nodes between them (`through`: the node types
+    that may lie between, None = any node with one child)"""
     while node is not None:
         if isinstance(node, (AggregateExec, GpuFusedAggregateExec)):
             return node if node.mode == "Partial" else None
+        if through is not None and not isinstance(node, through):
+            return None
         kids = node.children()
         node = kids[0] if len(kids) == 1 else None
     return None
+
+
+_EXCHANGE_NODES = (RepartitionExec, CoalesceBatchesExec, CoalescePartitionsExec, SortPreservingMergeExec)
+
+
+def _has_distinct(node) -> bool:
+    return any(f in ops.DISTINCT_FUNCS for f, _, _, _ in ops.normalize_aggs(node.aggr_expr))
 
 
 def _aggr_detail(aggr_expr):
@@ -834,7 +844,17 @@ class GpuOffloadRule:
         return True
 
     def optimize(self, plan: ExecutionPlan) -> ExecutionPlan:
-        return self._rewrite(plan, parent_needs_order=True)
+        plan = self._rewrite(plan, parent_needs_order=True)
+        self._decline_orphan_partials(plan)
+        return plan
+
+    def _decline_orphan_partials(self, node: ExecutionPlan):
+        """a Partial node with a DISTINCT aggregate that no Final parent collapsed (see _rewrite) stays the reference's operator"""
+        if isinstance(node, AggregateExec) and node.mode == "Partial" and _has_distinct(node) and not getattr(node, "kept_on_cpu", False):
+            node.kept_on_cpu = True
+            self.declined.append((node, unsupported_reason(node)))
+        for c in node.children():
+            self._decline_orphan_partials(c)
 
     # transform_up: children first (tree_node.rs), then this node.  `needs_order` = some ancestor observes this
     # node's output order (maintains_input_order / required_input_ordering in the reference's terms)
@@ -867,6 +887,30 @@ class GpuOffloadRule:
             node.kept_on_cpu = True
             self.declined.append((node, f"{node.name()} on {self.world_size} ranks: the nested loop join is only exercised on one rank"))
             return node
+        if isinstance(node, AggregateExec) and self.world_size == 1 and _has_distinct(node) and not getattr(node, "kept_on_cpu", False):
+            # DISTINCT aggregates have no device partial state.  On one rank the exchange between Final and Partial is gone already and
+            # Final o Partial == Single: the Partial is left as it is when it is visited, and the pair becomes ONE Single node — the
+            # Partial's expressions over the Partial's input, the Final's output names — when its Final parent is
+            if node.mode == "Partial":
+                return node
+            # (only through the exchange and bookkeeping nodes, which mean nothing on one rank: a filter, limit or sort between the two
+            # would be lost with them, so such a pair is declined like any staged DISTINCT aggregate)
+            below = _partial_below(node.input, _EXCHANGE_NODES) if node.mode in ("Final", "FinalPartitioned") else None
+            if below is not None and isinstance(below, AggregateExec) and not getattr(below, "kept_on_cpu", False) \
+                    and len(below.group_by) == len(node.group_by) and len(below.aggr_expr) == len(node.aggr_expr):
+                gb = [(e, n) for (e, _), (_, n) in zip(below.group_by, node.group_by)]
+                aggs = [(f, e, fin[2]) if flt is None else (f, e, fin[2], flt)
+                        for (f, e, _, flt), fin in zip(ops.normalize_aggs(below.aggr_expr), ops.normalize_aggs(node.aggr_expr))]
+                single = AggregateExec("Single", gb, aggs, below.input)
+                try:
+                    reason = unsupported_reason(single)
+                except Exception:  # noqa: BLE001 - as below: a plan this layer cannot type is decided at run time
+                    reason = None
+                if reason is not None:                         # (an argument type the device refuses: the pair stays as it was)
+                    node.kept_on_cpu = below.kept_on_cpu = True
+                    self.declined.append((node, reason))
+                    return node
+                node = single                                  # and on through the usual handling of a Single node
         if not isinstance(node, (GpuHashJoinExec, GpuFusedAggregateExec)) and not getattr(node, "kept_on_cpu", False):
             try:
                 reason = unsupported_reason(node)
@@ -1076,15 +1120,26 @@ def _sum_type(t):
 
 def _agg_type(func, t):
     import pyarrow as pa
-    if func == "count":
+    if func in ("count", "count_distinct"):
         return pa.int64()
-    if func == "sum":
+    if func in ("sum", "sum_distinct"):
         return _sum_type(t)
     if func == "avg":
         return pa.decimal128(min(38, t.precision + 4), min(38, t.scale + 4)) if pa.types.is_decimal128(t) else pa.float64()   # average.rs:219-252
     if func in ops.VARIANCE_FUNCS:
         return pa.float64()     # variance.rs / stddev.rs return_type
     return t    # min / max; bit_and / bit_or / bit_xor and bool_and / bool_or: the argument's type (bit_and_or_xor.rs, bool_and_or.rs)
+
+
+def _device_type_name(t):
+    """runtime.hip type_name: how the library's messages spell a column type.  A type the device does not have (no table holds one) is
+    spelled as pyarrow spells it."""
+    import pyarrow as pa
+    if pa.types.is_decimal128(t):
+        return f"Decimal128({t.precision},{t.scale})"
+    names = {pa.int32(): "Int32", pa.int64(): "Int64", pa.float64(): "Float64", pa.uint8(): "UInt8", pa.uint32(): "UInt32", pa.uint64(): "UInt64",
+             pa.date32(): "Date32", pa.bool_(): "Boolean"}
+    return names.get(t, str(t))
 
 
 def _key_bits(t):
@@ -1103,6 +1158,14 @@ def unsupported_reason(node):
     meets them at run time (the DFGPU_CHECKs named below); the rule asks first, so that such an operator STAYS the reference's CPU
     operator instead of failing the query — every entry here has a test that feeds a plan through GpuOffloadRule."""
     import pyarrow as pa
+    if isinstance(node, (AggregateExec, GpuFusedAggregateExec)):
+        # aggregate.hip dfgpu_agg_create: a DISTINCT aggregate's partial state is a List column in the reference, so the device takes
+        # the single-stage modes only (known without typing anything: a plan without a device is told the same)
+        for func, e, n, _ in ops.normalize_aggs(node.aggr_expr):
+            if func in ops.DISTINCT_FUNCS and e is None:
+                return f"{ops.DISTINCT_NAMES[func]} (aggregate {n}) needs an argument"
+            if func in ops.DISTINCT_FUNCS and node.mode not in ("Single", "SinglePartitioned"):
+                return f"{ops.DISTINCT_NAMES[func]} (aggregate {n}) is not supported in mode {node.mode} on the GPU path: its partial state is a List column"
     if isinstance(node, (AggregateExec, GpuFusedAggregateExec)) and node.mode in ("Single", "SinglePartitioned", "Partial"):
         inp = plan_schema(node.input)
         if inp is None:
@@ -1131,6 +1194,19 @@ def unsupported_reason(node):
                     return f"{func}({e!r}): {err}"
                 except (KeyError, TypeError, ValueError):
                     continue   # not typable from this schema (a name the input does not carry): decided at run time
+                if func in ops.DISTINCT_FUNCS:
+                    # aggregate.hip distinct_check_type, in its words (type_name's spelling for every type the device has)
+                    what, stringy = ops.DISTINCT_NAMES[func], pa.types.is_string(t) or pa.types.is_large_string(t) or pa.types.is_dictionary(t)
+                    summable = pa.types.is_decimal128(t) or t in (pa.int32(), pa.int64(), pa.uint8(), pa.uint32(), pa.uint64())
+                    if pa.types.is_boolean(t):
+                        return f"{what} over Boolean is not supported on the GPU path"
+                    if func == "sum_distinct" and stringy:
+                        return f"{what} over Utf8 is not supported on the GPU path"
+                    if func == "sum_distinct" and t == pa.float64():
+                        return f"{what} over Float64 is not supported on the GPU path"
+                    if not (summable or (func == "count_distinct" and (stringy or t in (pa.date32(), pa.float64())))):
+                        return f"{what} over {_device_type_name(t)} is not supported on the GPU path"
+                    continue
                 if func == "avg" and pa.types.is_decimal128(t) and t.precision + 13 > 38:
                     # aggregate.hip avg_sum_type: avg_sum_data_type (average.rs:131-172) widens to Decimal256 beyond 38 digits
                     return f"AVG({n}) over {t} accumulates in Decimal256 in the reference (no device representation)"

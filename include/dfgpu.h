@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define DFGPU_ABI_VERSION 20
+#define DFGPU_ABI_VERSION 21
 
 /* Arrow C Data Interface (https://arrow.apache.org/docs/format/CDataInterface.html) */
 #ifndef ARROW_C_DATA_INTERFACE
@@ -615,17 +615,36 @@ typedef enum dfgpu_agg_mode {
  * BIT_AND .. BIT_XOR (ABI 15): bit_and_or_xor.rs — registered names bit_and, bit_or, bit_xor; the argument is Int32, Int64, UInt8,
  * UInt32 or UInt64, the result the argument's type.  BOOL_AND / BOOL_OR (ABI 15): bool_and_or.rs — bool_and, bool_or; argument and
  * result are Boolean.  NULL arguments are skipped; a group without a non-NULL value gives NULL.  Any other argument type is refused
- * ("... is not supported on the GPU path"); DISTINCT and ORDER BY inside an aggregate are not taken.
+ * ("... is not supported on the GPU path"); ORDER BY inside an aggregate is not taken, DISTINCT only as the two functions below.
  * FILTER (ABI 16): AggregateExec::filter_expr, one optional Boolean expression per aggregate, handed to GroupsAccumulator::update_batch
  * as opt_filter — a row reaches the aggregate only where its filter is TRUE (FALSE and NULL exclude it).  Filters never decide which
  * groups exist: a group none of whose rows pass gives the aggregate's "nothing seen" value (NULL; 0 for COUNT).  COUNT(*) FILTER counts
  * the rows where the filter is TRUE.  Raw modes only (Partial / Single / SinglePartitioned, grouping sets included): in Final,
  * FinalPartitioned and PartialReduce a filter is ignored like `arg`, and the partial-state schema is that of the unfiltered aggregate.
- * A filter that is not Boolean is an error of the first update, which names the aggregate. */
+ * A filter that is not Boolean is an error of the first update, which names the aggregate.
+ * COUNT_DISTINCT / SUM_DISTINCT (ABI 21): an aggregate whose AggregateFunctionExpr is_distinct — the argument travels in `arg`, the
+ * optional filter in `filter`.  The node keeps a device-resident set of (group, value bits) per argument for its whole life.
+ *   COUNT(DISTINCT x): Int64, never NULL — the number of different non-NULL values of x in the group, 0 for a group that saw none;
+ *     over no rows without GROUP BY one row, 0.  x is Int32, Int64, UInt8, UInt32, UInt64, Date32, Decimal128, Float64 or a string.
+ *     Float64 values are different when their bit patterns are (the reference's Hashable<T>): +0.0 and -0.0 are two values, two NaNs
+ *     with different payloads are two values, the same NaN is one.
+ *   SUM(DISTINCT x): the sum of the different non-NULL values in SUM's result type for x, wrapping as SUM wraps; NULL for a group that
+ *     saw none.  x is Int32, Int64, UInt8, UInt32, UInt64 or Decimal128.  Float64 is refused ("SUM(DISTINCT) over Float64 is not
+ *     supported on the GPU path"): its sum depends on the order of the set.
+ *   Boolean arguments (bit-packed) are refused ("... over Boolean is not supported on the GPU path"), and so is a spec without an
+ *     argument, by name.
+ *   Strings: a plain Utf8 column is interned on entry, as Utf8 group keys are, and its codes are counted; the codes of a dictionary-
+ *     encoded column are counted after the dictionary's values have been made unique (an imported dictionary may repeat a value).  As
+ *     for Utf8 keys, a string argument takes one update per node unless the dictionary stays the same.
+ *   FILTER: the argument is NULL where the filter is not TRUE; a group none of whose rows pass gives 0 / NULL and still exists.
+ *   Modes: Single and SinglePartitioned.  The reference's partial state of a DISTINCT aggregate is a List column, which has no device
+ *     form: Partial, Final, FinalPartitioned and PartialReduce with such an aggregate are refused by dfgpu_agg_create, and any mode by
+ *     dfgpu_agg_create_grouping_sets, with a message that names the aggregate (and the mode). */
 typedef enum dfgpu_agg_func {
   DFGPU_AGG_SUM = 0, DFGPU_AGG_MIN = 1, DFGPU_AGG_MAX = 2, DFGPU_AGG_COUNT = 3, DFGPU_AGG_AVG = 4,
   DFGPU_AGG_VAR_SAMP = 5, DFGPU_AGG_VAR_POP = 6, DFGPU_AGG_STDDEV_SAMP = 7, DFGPU_AGG_STDDEV_POP = 8,
-  DFGPU_AGG_BIT_AND = 9, DFGPU_AGG_BIT_OR = 10, DFGPU_AGG_BIT_XOR = 11, DFGPU_AGG_BOOL_AND = 12, DFGPU_AGG_BOOL_OR = 13
+  DFGPU_AGG_BIT_AND = 9, DFGPU_AGG_BIT_OR = 10, DFGPU_AGG_BIT_XOR = 11, DFGPU_AGG_BOOL_AND = 12, DFGPU_AGG_BOOL_OR = 13,
+  DFGPU_AGG_COUNT_DISTINCT = 14, DFGPU_AGG_SUM_DISTINCT = 15
 } dfgpu_agg_func;
 typedef struct dfgpu_agg_spec {
   int32_t func;          /* dfgpu_agg_func */
@@ -680,6 +699,7 @@ int dfgpu_agg_fused_updates(dfgpu_agg_t h, int64_t* out);
  *   jit.strict = 0|1 (0)                a failed specialisation is an error instead of a fall-back to the interpreter
  *   jit.cache = 0|1 (1), jit.cache_dir  on-disk cache of compiled nodes; jit.dump_dir: generated sources are written there
  *   agg.partitioned = 0|1 (1), agg.partitioned_min_rows (2 x rows worth a pass), agg.grouped_move, agg.direct_table, agg.runs = 0|1 (1)
+ *   agg.distinct_slots (test hook: 0 = derived; the slots a DISTINCT aggregate's set starts with: 64 makes small inputs grow it)
  *   join.grouped_probe = 0|1 (1), join.grouped_min_rows (rows worth a pass), join.beyond_cache_bytes (4 x the L2 of an XCD),
  *   join.grouped_bits, join.near_window (test hooks: 0 = derived)
  *   join.share_probe = 0|1 (1: an all-hit probe in probe order hands back the probe table's own columns, dfgpu_join_probe),
