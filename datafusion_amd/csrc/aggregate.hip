@@ -1181,6 +1181,151 @@ __global__ __launch_bounds__(BLOCK) void k_distinct_reduce(DistinctDev s, uint32
   }
 }
 
+// ------------------------------------------------------------------------------- MEDIAN
+// MEDIAN is holistic: a group has no fixed-size cell, so the node keeps every non-NULL argument row — (group number, orderable value) —
+// in a row store that lives as long as the node, and sorts it when it emits.  An orderable key is the value's bits transformed so that
+// UNSIGNED comparison of keys is the type's order: signed integers with their sign bit flipped, Float64 by the IEEE totalOrder
+// transform (negative: every bit flipped, else the sign bit set), Decimal128 as (lo, hi with the sign bit flipped).  The radix passes
+// (sort.hip) then need to know nothing about the type, and Int32 / UInt32 / UInt8 keys take 32 / 32 / 8 bits of passes instead of 64.
+struct MedianDev {
+  uint32_t* gid;
+  unsigned long long* lo;
+  unsigned long long* hi;   // Decimal128 only, else null
+  uint32_t* count;          // rows stored
+};
+__device__ __forceinline__ void median_orderable(int type, uint64_t& lo, uint64_t& hi) {
+  switch (type) {
+    case DFGPU_INT32: lo = (uint64_t)((uint32_t)lo ^ 0x80000000u); hi = 0; break;
+    case DFGPU_INT64: lo ^= 1ull << 63; hi = 0; break;
+    case DFGPU_FLOAT64: lo ^= (lo >> 63) ? ~0ull : 1ull << 63; hi = 0; break;
+    case DFGPU_DECIMAL128: hi ^= 1ull << 63; break;
+    default: hi = 0; break;   // UInt8 / UInt32 / UInt64: the value itself
+  }
+}
+// back to the value's bits (Int32: sign-extended to 64)
+__device__ __forceinline__ void median_value(int type, uint64_t& lo, uint64_t& hi) {
+  switch (type) {
+    case DFGPU_INT32: lo = (uint64_t)(int64_t)(int32_t)((uint32_t)lo ^ 0x80000000u); break;
+    case DFGPU_INT64: lo ^= 1ull << 63; break;
+    case DFGPU_FLOAT64: lo = (lo >> 63) ? lo ^ (1ull << 63) : ~lo; break;
+    case DFGPU_DECIMAL128: hi ^= 1ull << 63; break;
+    default: break;
+  }
+}
+// Every non-NULL row of the argument column (a FILTER is folded into its validity already) is stored.  A wave asks for its positions
+// with ONE atomicAdd: the ballot of the rows that have a value, its popcount for the counter, a lane's rank among the set bits for
+// its position — so a wave's stores are consecutive elements of each array.  The order inside the store is free.  `cap`: the
+// elements the arrays hold (the host reserved stored + n before the launch; the guard costs nothing beside the stores)
+__global__ __launch_bounds__(BLOCK) void k_median_append(InternCtx c, const uint32_t* __restrict__ slot_gid, int has_groups, int64_t row_offset, int64_t n, AccDesc d, int type,
+                                                        MedianDev s, uint32_t cap) {
+  const unsigned lane = lane_id();
+  for (int64_t base = (int64_t)blockIdx.x * BLOCK; base < n; base += (int64_t)gridDim.x * BLOCK) {   // (`base`: the same in every lane of a wave)
+    const int64_t i = base + threadIdx.x;
+    const bool has = i < n && (!d.valid || bit_at(d.valid, i));
+    const uint64_t m = ballot64(has);
+    if (m == 0) continue;
+    const int leader = __builtin_ctzll(m);
+    uint32_t first = 0;
+    if ((int)lane == leader) first = atomicAdd(s.count, (uint32_t)__popcll(m));
+    first = (uint32_t)__shfl((int)first, leader);
+    if (!has) continue;
+    uint64_t lo, hi;
+    load_value(d, i, lo, hi);
+    median_orderable(type, lo, hi);
+    const uint32_t pos = first + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    if (pos >= cap) continue;
+    s.gid[pos] = has_groups ? lookup_gid(c, slot_gid, row_offset + i) : 0u;
+    s.lo[pos] = lo;
+    if (s.hi) s.hi[pos] = hi;
+  }
+}
+// counts[g] = stored rows of group g.  Few groups: a workgroup counts in LDS and adds what it found once; many groups: an atomic per
+// row, a wave whose rows are all of one group (a group that holds much of the store) adds once
+constexpr int MEDIAN_LDS_GROUPS = 4096;
+__global__ __launch_bounds__(BLOCK) void k_median_count(const uint32_t* __restrict__ gid, uint32_t m, uint32_t G, uint32_t* __restrict__ counts) {
+  __shared__ uint32_t h[MEDIAN_LDS_GROUPS];
+  const bool lds = G <= (uint32_t)MEDIAN_LDS_GROUPS;
+  if (lds) {
+    for (uint32_t g = threadIdx.x; g < G; g += BLOCK) h[g] = 0u;
+    __syncthreads();
+  }
+  for (uint32_t base = blockIdx.x * BLOCK; base < m; base += gridDim.x * BLOCK) {
+    const uint32_t j = base + threadIdx.x;
+    const bool in = j < m;
+    const uint32_t g = in ? gid[j] : 0u;
+    if (lds) {
+      if (in && g < G) atomicAdd(&h[g], 1u);
+      continue;
+    }
+    const uint64_t live = ballot64(in);
+    if (live == 0) continue;
+    const uint32_t g0 = (uint32_t)__shfl((int)g, __builtin_ctzll(live));
+    if (ballot64(in && g == g0) == live) {
+      if (lane_id() == (unsigned)__builtin_ctzll(live) && g0 < G) atomicAdd(&counts[g0], (uint32_t)__popcll(live));
+    } else if (in && g < G) {
+      atomicAdd(&counts[g], 1u);
+    }
+  }
+  if (lds) {
+    __syncthreads();
+    for (uint32_t g = threadIdx.x; g < G; g += BLOCK)
+      if (h[g]) atomicAdd(&counts[g], h[g]);
+  }
+}
+// the next pass's keys in the order the passes so far left the rows in: key[j] = gid[idx[j]] (the group pass) or hi[idx[j]] (Decimal128)
+__global__ __launch_bounds__(BLOCK) void k_median_gather_keys(const uint32_t* __restrict__ idx, uint32_t m, const uint32_t* __restrict__ src32,
+                                                             const unsigned long long* __restrict__ src64, unsigned long long* __restrict__ key) {
+  for (uint32_t j = blockIdx.x * BLOCK + threadIdx.x; j < m; j += gridDim.x * BLOCK) key[j] = src32 ? (unsigned long long)src32[idx[j]] : src64[idx[j]];
+}
+// A lane per group: idx is in (group, value) order, so group g's values are idx[o .. o + c) ascending, o = offsets[g], c = counts[g].
+// c odd: the middle one, its bits unchanged.  c even: (lower middle + upper middle) / 2 in the argument's OWN type — the sum wraps at
+// the type's width (add_wrapping), the division truncates toward zero (div_wrapping); Float64: one IEEE addition, one IEEE division.
+// The cells are written in the form the emit hands out for the type: the value sign- / zero-extended in lo (Int32: what MIN keeps),
+// Float64 as f64_ordered, Decimal128 in lo and hi
+__global__ __launch_bounds__(BLOCK) void k_median_pick(MedianDev s, uint32_t m, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ counts,
+                                                      const uint64_t* __restrict__ offsets, int64_t G, int type, unsigned long long* __restrict__ out_lo,
+                                                      unsigned long long* __restrict__ out_hi, uint32_t* __restrict__ seen) {
+  for (int64_t g = (int64_t)blockIdx.x * BLOCK + threadIdx.x; g < G; g += (int64_t)gridDim.x * BLOCK) {
+    const uint64_t cnt = counts[g], o = offsets[g];
+    if (cnt == 0 || o + cnt > m) {   // (no value: NULL.  The second test cannot fail: counts and offsets are made from this store)
+      seen[g] = 0u;
+      continue;
+    }
+    const uint32_t ja = idx[o + (cnt - 1) / 2], jb = idx[o + cnt / 2];
+    uint64_t alo = s.lo[ja], ahi = s.hi ? s.hi[ja] : 0ull;
+    median_value(type, alo, ahi);
+    uint64_t rlo = alo, rhi = ahi;
+    if ((cnt & 1ull) == 0) {
+      uint64_t blo = s.lo[jb], bhi = s.hi ? s.hi[jb] : 0ull;
+      median_value(type, blo, bhi);
+      switch (type) {
+        case DFGPU_INT32: rlo = (uint64_t)(int64_t)((int32_t)((uint32_t)alo + (uint32_t)blo) / 2); break;
+        case DFGPU_INT64: rlo = (uint64_t)((int64_t)(alo + blo) / 2); break;
+        case DFGPU_UINT8: rlo = (uint64_t)((uint8_t)((uint8_t)alo + (uint8_t)blo) / 2u); break;
+        case DFGPU_UINT32: rlo = (uint64_t)(((uint32_t)alo + (uint32_t)blo) / 2u); break;
+        case DFGPU_UINT64: rlo = (alo + blo) / 2ull; break;
+        case DFGPU_FLOAT64: {
+          const double sum = __longlong_as_double((long long)alo) + __longlong_as_double((long long)blo);
+          rlo = (uint64_t)__double_as_longlong(sum / 2.0);
+          break;
+        }
+        case DFGPU_DECIMAL128: {
+          const u128 sum = (((u128)ahi << 64) | (u128)alo) + (((u128)bhi << 64) | (u128)blo);
+          const i128 r = (i128)sum / 2;
+          rlo = (uint64_t)(u128)r;
+          rhi = (uint64_t)((u128)r >> 64);
+          break;
+        }
+        default: break;
+      }
+    }
+    if (type == DFGPU_FLOAT64) rlo = (uint64_t)((int64_t)rlo ^ (int64_t)((uint64_t)((int64_t)rlo >> 63) >> 1));   // (f64_ordered of the bits)
+    out_lo[g] = rlo;
+    if (out_hi) out_hi[g] = rhi;
+    seen[g] = 1u;
+  }
+}
+
 // ------------------------------------------------------------------------------- host
 // the set of one DISTINCT argument (shared by the aggregates of a node over the same argument expression and filter)
 struct DistinctSet {
@@ -1204,6 +1349,18 @@ struct DistinctSet {
                        wide ? e_hi->as<unsigned long long>() : nullptr, count->as<uint32_t>()};
   }
 };
+// the row store of one MEDIAN argument (shared by the aggregates of a node over the same argument expression and filter)
+struct MedianStore {
+  bool typed = false;
+  dfgpu_field type{};          // the argument's column type
+  bool wide = false;           // Decimal128: 128 value bits
+  BufPtr gid, lo, hi;
+  int64_t cap = 0;             // elements of the store
+  int64_t stored = 0;          // as read back after the last update
+  BufPtr count;
+  std::shared_ptr<PinnedBuf> count_host;
+  MedianDev dev() const { return MedianDev{gid->as<uint32_t>(), lo->as<unsigned long long>(), wide ? hi->as<unsigned long long>() : nullptr, count->as<uint32_t>()}; }
+};
 struct AggState {
   int func;               // dfgpu_agg_func
   bool has_arg;
@@ -1226,6 +1383,7 @@ struct AggState {
   BufPtr lo, hi, seen;    // primary accumulator (sum / min / max / count)
   BufPtr cnt;             // AVG: row count
   std::shared_ptr<DistinctSet> dset;   // COUNT / SUM(DISTINCT): the set; lo / hi / seen are filled from it when the node emits
+  std::shared_ptr<MedianStore> mstore; // MEDIAN: the row store; lo / hi / seen likewise
   // SUM over Decimal128 written by the ordered-input runs node as the first update: {lo, hi} side by side, 16 bytes per group —
   // the Decimal128 column itself, which emit hands out as it is (the lo / hi arrays would cost a 2 x 8 -> 16 byte pass over
   // every group: 1.0 of the 7.2 ms of GROUP BY l_orderkey at SF100).  lo / hi are stale while this is set; the next update
@@ -1464,6 +1622,125 @@ static void distinct_insert(DistinctSet& ds, const InternCtx& ictx, const uint32
   DFGPU_HIP(hipMemcpyAsync(ds.count_host->ptr, ds.count->ptr, 4, hipMemcpyDeviceToHost, r.stream));
 }
 
+// ---- MEDIAN: the host side of the row store (kernels: behind the DISTINCT block)
+static bool is_holistic(int func) { return func == DFGPU_AGG_MEDIAN; }
+// an aggregate without a cell per group while the node is updated: its cells are made when the node emits
+static bool cells_at_emit(int func) { return is_distinct(func) || is_holistic(func); }
+constexpr int64_t MEDIAN_MAX_ROWS = 0x7FFFFFFEll;   // 2^31 - 2: the sort's row ids are 32 bits
+// the argument types of include/dfgpu.h, refused in distinct_check_type's spelling
+static void median_check_type(const Column& v) {
+  const int t = v.field.type;
+  DFGPU_CHECK(t != DFGPU_BOOL, "MEDIAN over Boolean is not supported on the GPU path");
+  DFGPU_CHECK(t != DFGPU_UTF8 && !v.dict, "MEDIAN over Utf8 is not supported on the GPU path");
+  const bool numeric = t == DFGPU_INT32 || t == DFGPU_INT64 || t == DFGPU_UINT8 || t == DFGPU_UINT32 || t == DFGPU_UINT64 || t == DFGPU_FLOAT64 || t == DFGPU_DECIMAL128;
+  DFGPU_CHECK(numeric, "MEDIAN over " + type_name(v.field) + " is not supported on the GPU path");
+}
+// the bits of a type's orderable key that can differ: what the value passes of the sort run over
+static int median_key_bits(int type) { return type == DFGPU_UINT8 ? 8 : type == DFGPU_INT32 || type == DFGPU_UINT32 ? 32 : 64; }
+// binds the store to its argument's type on the first update that has rows and holds later ones to it
+static void median_bind(MedianStore& ms, const Column& v, const std::string& name) {
+  if (ms.typed) {
+    DFGPU_CHECK(ms.type.type == v.field.type && ms.type.precision == v.field.precision && ms.type.scale == v.field.scale,
+                "aggregate " + name + ": the argument's type changed between updates");
+    return;
+  }
+  ms.typed = true;
+  ms.type = v.field;
+  ms.wide = v.field.type == DFGPU_DECIMAL128;
+}
+// before an update of n rows: room for stored + n values, growing by doubling with a device copy (agg.median_rows: a test's way to
+// start small).  The bytes are admitted by the pool first: a size it cannot take fails with its message
+static void median_reserve(MedianStore& ms, int64_t n, const std::string& name) {
+  Runtime& r = rt();
+  const int64_t need = ms.stored + n;
+  DFGPU_CHECK(need <= MEDIAN_MAX_ROWS, "MEDIAN (aggregate " + name + ") would hold " + std::to_string(need) +
+                                           " values: more than 2^31 - 2 are not supported on the GPU path (the sort's row ids are 32 bits)");
+  if (!ms.count) {
+    ms.count = make_zero_buf(16);
+    ms.count_host = std::make_shared<PinnedBuf>(16);
+  }
+  if (need <= ms.cap) return;
+  int64_t cap = ms.cap ? 2 * ms.cap : option_int("agg.median_rows", 0);
+  cap = std::min(std::max(cap, need), MEDIAN_MAX_ROWS);
+  pool_admit(cap * (4 + 8 + (ms.wide ? 8 : 0)));
+  auto regrow = [&](BufPtr& b, int elem) {
+    BufPtr nb = make_buf((size_t)cap * elem);
+    if (b && ms.stored) DFGPU_HIP(hipMemcpyAsync(nb->ptr, b->ptr, (size_t)ms.stored * elem, hipMemcpyDeviceToDevice, r.stream));
+    b = nb;
+  };
+  regrow(ms.gid, 4);
+  regrow(ms.lo, 8);
+  if (ms.wide) regrow(ms.hi, 8);
+  ms.cap = cap;
+}
+// the batch's non-NULL rows into the store; the count follows the kernel to the host and is read after the update's final wait
+static void median_append(MedianStore& ms, const InternCtx& ictx, const uint32_t* slot_gid, bool has_groups, int64_t row_offset, int64_t n, const Column& v) {
+  Runtime& r = rt();
+  AccDesc d{};
+  d.values = v.ptr();
+  d.valid = v.valid_words();
+  d.val = distinct_val_kind(ms.type.type);   // (the value's bits; Int32 sign-extended)
+  {
+    ProfileScope ps("agg_median_append", n * (type_width(ms.type.type) + 4) + n * (ms.wide ? 20 : 12));
+    k_median_append<<<std::min(grid_for(n, BLOCK), 8192), BLOCK, 0, r.stream>>>(ictx, slot_gid, has_groups ? 1 : 0, row_offset, n, d, ms.type.type, ms.dev(), (uint32_t)ms.cap);
+    DFGPU_HIP(hipGetLastError());
+  }
+  DFGPU_HIP(hipMemcpyAsync(ms.count_host->ptr, ms.count->ptr, 4, hipMemcpyDeviceToHost, r.stream));
+}
+// the cells of the aggregates over this store, made from nothing: count the groups' rows, sort the row ids by (group, value) — the
+// value passes first, the group pass last: the passes are stable — and pick each group's middle
+static void median_emit(const MedianStore& ms, int64_t G, bool has_groups, bool needs_hi, BufPtr& lo, BufPtr& hi, BufPtr& seen) {
+  Runtime& r = rt();
+  const int64_t Gc = G ? G : 1;
+  lo = make_zero_buf((size_t)Gc * 8);
+  hi = needs_hi ? make_zero_buf((size_t)Gc * 8) : nullptr;   // (by the aggregate's type, not the store's: a store that saw no batch has no type, the emit reads hi all the same)
+  seen = make_zero_buf((size_t)Gc * 4);
+  const int64_t m = ms.stored;
+  if (m == 0 || G == 0) return;
+  const int type = ms.type.type;
+  // the sort's temporaries, for the duration of this call: keys and ids, double-buffered
+  // (and the passes' per-tile digit counts and offsets: 256 x 12 bytes per 4 096-row tile)
+  pool_admit(2 * m * (8 + 4) + (m / 4096 + 1) * 256 * 12 + G * 4 + (G + 1) * 8);
+  const MedianDev s = ms.dev();
+  const int grid_m = std::min(grid_for(m, BLOCK), 4096);
+  BufPtr counts = make_zero_buf((size_t)G * 4), offsets = make_buf((size_t)(G + 1) * 8);
+  {
+    ProfileScope ps("agg_median_count", m * 4 + G * 8);
+    k_median_count<<<grid_m, BLOCK, 0, r.stream>>>(s.gid, (uint32_t)m, (uint32_t)G, counts->as<uint32_t>());
+    DFGPU_HIP(hipGetLastError());
+  }
+  scan_u32(counts->as<uint32_t>(), G, offsets->as<uint64_t>());
+  // the first pass reads the store's own keys where they lie (keep_input: no pass writes into them)
+  BufPtr key = ms.lo, idx;
+  radix_sort_pairs(key, idx, m, 0, median_key_bits(type), /*keep_input=*/true);
+  if (ms.wide) {
+    key = make_buf((size_t)m * 8);
+    {
+      ProfileScope ps("agg_median_hi_keys", m * (4 + 8 + 8));
+      k_median_gather_keys<<<grid_m, BLOCK, 0, r.stream>>>(idx->as<uint32_t>(), (uint32_t)m, nullptr, s.hi, key->as<unsigned long long>());
+      DFGPU_HIP(hipGetLastError());
+    }
+    radix_sort_pairs(key, idx, m, 0, 64);
+  }
+  if (has_groups && G > 1) {
+    int gbits = 0;
+    while (((int64_t)1 << gbits) < G) gbits++;
+    key = make_buf((size_t)m * 8);
+    {
+      ProfileScope ps("agg_median_gid_keys", m * (4 + 4 + 8));
+      k_median_gather_keys<<<grid_m, BLOCK, 0, r.stream>>>(idx->as<uint32_t>(), (uint32_t)m, s.gid, nullptr, key->as<unsigned long long>());
+      DFGPU_HIP(hipGetLastError());
+    }
+    radix_sort_pairs(key, idx, m, 0, gbits);
+  }
+  {
+    ProfileScope ps("agg_median_pick", G * (4 + 8 + 2 * (4 + (ms.wide ? 16 : 8)) + (ms.wide ? 16 : 8) + 4));
+    k_median_pick<<<std::min(grid_for(G, BLOCK), 4096), BLOCK, 0, r.stream>>>(s, (uint32_t)m, idx->as<uint32_t>(), counts->as<uint32_t>(), offsets->as<uint64_t>(), G, type,
+                                                                            lo->as<unsigned long long>(), hi ? hi->as<unsigned long long>() : nullptr, seen->as<uint32_t>());
+    DFGPU_HIP(hipGetLastError());
+  }
+}
+
 // what one aggregate accumulates, given its input column type
 struct AccPlan {
   int kind, val;
@@ -1488,6 +1765,19 @@ static AccPlan plan_for(int func, const dfgpu_field& t, bool merging_counts) {
     case DFGPU_AGG_SUM_DISTINCT:
       DFGPU_CHECK(t.type != DFGPU_FLOAT64, "SUM(DISTINCT) over Float64 is not supported on the GPU path");
       return plan_for(DFGPU_AGG_SUM, t, false);
+    // MEDIAN: nothing accumulates per row; the cells are filled from the row store when the node emits (k_median_pick), in the form
+    // the emit hands out for the type — MIN's, except that Decimal128 keeps all 128 bits in lo and hi
+    case DFGPU_AGG_MEDIAN:
+      switch (t.type) {
+        case DFGPU_INT32: return {ACC_MIN_I64, VAL_I32, false};
+        case DFGPU_INT64: return {ACC_MIN_I64, VAL_I64, false};
+        case DFGPU_UINT8: return {ACC_MIN_I64, VAL_U8, false};
+        case DFGPU_UINT32: return {ACC_MIN_I64, VAL_U32, false};
+        case DFGPU_UINT64: return {ACC_MIN_I64, VAL_U64, false};
+        case DFGPU_FLOAT64: return {ACC_MIN_I64, VAL_F64_ORDERED, false};
+        case DFGPU_DECIMAL128: return {ACC_SUM_I128, VAL_I128, true};
+      }
+      throw Error("MEDIAN over " + type_name(t) + " is not supported on the GPU path");
     case DFGPU_AGG_COUNT:
       // Final modes merge partial counts by summing them (count.rs merge_batch)
       if (merging_counts) return {ACC_SUM_I64, t.type == DFGPU_UINT64 ? VAL_U64 : VAL_I64, false};
@@ -2272,7 +2562,7 @@ static std::vector<AccPlan> grow_accumulators(Aggregate& A, int64_t G0, int64_t 
     for (AggState& a : A.aggs) {
       AccPlan p = plan_for(a.func, a.in_type, final_mode);
       plans.push_back(p);
-      if (is_distinct(a.func)) continue;   // (its cells exist from emit on)
+      if (cells_at_emit(a.func)) continue;   // (its cells exist from emit on)
       fresh(a.lo, acc_identity(p.kind), 8);
       if (p.needs_hi) fresh(a.hi, 0ull, 8);
       fresh(a.seen, 0ull, 4);
@@ -2287,7 +2577,7 @@ static std::vector<AccPlan> grow_accumulators(Aggregate& A, int64_t G0, int64_t 
   for (AggState& a : A.aggs) {
     AccPlan p = plan_for(a.func, a.in_type, final_mode);
     plans.push_back(p);
-    if (is_distinct(a.func)) continue;
+    if (cells_at_emit(a.func)) continue;
     a.lo = grown(a.lo, G0, G1, acc_identity(p.kind), 8, init);
     if (p.needs_hi) a.hi = grown(a.hi, G0, G1, 0ull, 8, init);
     a.seen = grown(a.seen, G0, G1, 0, 4, init);
@@ -4703,6 +4993,11 @@ static bool agg_update_fused(Aggregate& A, const Table& in, const dfgpu_expr* pr
       return false;
     }
   for (const AggState& a : A.aggs)
+    if (is_holistic(a.func)) {
+      why = "MEDIAN keeps the rows of every group";
+      return false;
+    }
+  for (const AggState& a : A.aggs)
     if (a.has_arg && (a.func == DFGPU_AGG_MIN || a.func == DFGPU_AGG_MAX)) {
       dfgpu_expr e{a.nodes.data(), (int)a.nodes.size(), a.root};
       if (wide_minmax(a.func, expr_type(e, in))) {
@@ -4964,6 +5259,7 @@ static void agg_update_unfused(Aggregate& A, const Table& in) {
     }
     if (inputs[k].has_v && wide_minmax(a.func, inputs[k].v.field)) wide_minmax_values_fit(inputs[k].v, a.name);
     if (is_distinct(a.func)) distinct_check_type(a, inputs[k].v);
+    if (is_holistic(a.func)) median_check_type(inputs[k].v);
   }
   // DISTINCT: every set is bound to its argument (a Utf8 one interned) and given room for this batch; aggregates that share a set
   // share the work.  Done before anything changes the node: a refusal leaves it as it was
@@ -4978,6 +5274,18 @@ static void agg_update_unfused(Aggregate& A, const Table& in) {
     distinct_bind(*a.dset, inputs[k].v, a.name);
     distinct_reserve(*a.dset, n);
     dsets.emplace_back(a.dset.get(), k);
+  }
+  // MEDIAN: the same for every row store
+  std::vector<std::pair<MedianStore*, size_t>> msets;   // (store, the first aggregate that holds it)
+  for (size_t k = 0; k < A.aggs.size(); k++) {
+    AggState& a = A.aggs[k];
+    if (!is_holistic(a.func) || n == 0) continue;
+    bool listed = false;
+    for (auto& d : msets) listed |= d.first == a.mstore.get();
+    if (listed) continue;
+    median_bind(*a.mstore, inputs[k].v, a.name);
+    median_reserve(*a.mstore, n, a.name);
+    msets.emplace_back(a.mstore.get(), k);
   }
 
   // ---- intern (GroupValues::intern)
@@ -5000,7 +5308,7 @@ static void agg_update_unfused(Aggregate& A, const Table& in) {
   for (size_t k = 0; k < A.aggs.size(); k++) {
     AggState& a = A.aggs[k];
     const AccPlan& p = plans[k];
-    if (is_distinct(a.func)) continue;   // (no cell per group: the pass after the accumulation below)
+    if (cells_at_emit(a.func)) continue;   // (no cell per group: the pass after the accumulation below)
     if (is_variance(a.func)) {
       // pass 1 counts and sums this batch's values per group into fresh cells; pass 2 and the merge follow the accumulation below
       if (n == 0) continue;
@@ -5079,7 +5387,7 @@ static void agg_update_unfused(Aggregate& A, const Table& in) {
       accs.a[accs.n++] = c;
     }
   }
-  if (n == 0 || (accs.n == 0 && dsets.empty())) {
+  if (n == 0 || (accs.n == 0 && dsets.empty() && msets.empty())) {
     A.ngroups = G1;
     return;
   }
@@ -5090,7 +5398,7 @@ static void agg_update_unfused(Aggregate& A, const Table& in) {
   const int per_rep = std::max(1, accs.n) * (int)std::min<int64_t>(G1, LDS_CELLS + 1);
   const uint32_t* sg = IR.slot_gid ? IR.slot_gid->as<uint32_t>() : nullptr;
   if (accs.n == 0) {
-    // (DISTINCT aggregates only: nothing has a cell per group)
+    // (DISTINCT / MEDIAN aggregates only: nothing has a cell per group)
   } else if (G1 * accs.n <= LDS_CELLS) {
     int nrep = std::max(1, std::min(64, LDS_CELLS / per_rep));
     // power of two so that consecutive lanes spread over the replicas
@@ -5135,9 +5443,14 @@ static void agg_update_unfused(Aggregate& A, const Table& in) {
   }
   // COUNT / SUM(DISTINCT): this batch's (group, value) pairs into the sets, after the ordinary accumulators have run
   for (auto& d : dsets) distinct_insert(*d.first, ictx, sg, ngk > 0, G0, n, inputs[d.second].v);
+  // MEDIAN: this batch's non-NULL (group, value) rows into the row stores
+  for (auto& d : msets) median_append(*d.first, ictx, sg, ngk > 0, G0, n, inputs[d.second].v);
   A.ngroups = G1;
   DFGPU_HIP(hipStreamSynchronize(r.stream));  // temporaries (evaluated columns, tables) are released on return
   for (auto& d : dsets) d.first->entries = *reinterpret_cast<volatile uint32_t*>(d.first->count_host->ptr);   // (the count rode on that wait)
+  for (auto& d : msets) d.first->stored = *reinterpret_cast<volatile uint32_t*>(d.first->count_host->ptr);
+  // (the reserve before the launch makes room for every row; a count beyond the capacity would mean rows the kernel dropped)
+  for (auto& d : msets) DFGPU_CHECK(d.first->stored <= d.first->cap, "aggregate " + A.aggs[d.second].name + ": the MEDIAN row store counted more rows than it holds");
 }
 
 // aggregate_batch_inner over a whole table, optionally under a FilterExec predicate fused in front
@@ -5312,6 +5625,21 @@ static Table agg_emit(Aggregate& A) {
         DFGPU_HIP(hipGetLastError());
       }
     }
+    if (is_holistic(a.func)) {
+      // a MEDIAN's cells likewise: the store is counted, sorted and picked from once per emit, and the aggregates that share it share the cells
+      const AggState* twin = nullptr;
+      for (const AggState& b : A.aggs) {
+        if (&b == &a) break;
+        if (is_holistic(b.func) && b.mstore == a.mstore) twin = &b;
+      }
+      if (twin) {
+        a.lo = twin->lo;
+        a.hi = twin->hi;
+        a.seen = twin->seen;
+      } else {
+        median_emit(*a.mstore, G, ngk > 0, p.needs_hi, a.lo, a.hi, a.seen);
+      }
+    }
     // value type of the primary accumulator when emitted
     auto value_field = [&]() -> dfgpu_field {
       switch (a.func) {
@@ -5328,7 +5656,7 @@ static Table agg_emit(Aggregate& A) {
     else if (p.val == VAL_F64_ORDERED) mode = 2;
     else if (vf.type == DFGPU_INT32 || vf.type == DFGPU_DATE32) mode = 3;
     else if (vf.type == DFGPU_UINT8) mode = 4;
-    else if (is_bitwise(a.func) && vf.type == DFGPU_UINT32) mode = 3;   // (the low 32 bits of the cell)
+    else if ((is_bitwise(a.func) || is_holistic(a.func)) && vf.type == DFGPU_UINT32) mode = 3;   // (the low 32 bits of the cell)
     else if (is_bitwise(a.func) && vf.type == DFGPU_BOOL) mode = 6;
     if (is_variance(a.func)) {
       if (A.partial_out()) {
@@ -5464,12 +5792,12 @@ int dfgpu_agg_create(int mode, const dfgpu_expr* group_by, const char* const* gr
     for (int k = 0; k < n_aggs; k++) {
       AggState a;
       a.func = aggs[k].func;
-      DFGPU_CHECK(a.func >= DFGPU_AGG_SUM && a.func <= DFGPU_AGG_SUM_DISTINCT, "unsupported aggregate function");
+      DFGPU_CHECK(a.func >= DFGPU_AGG_SUM && a.func <= DFGPU_AGG_MEDIAN, "unsupported aggregate function");
       a.has_arg = aggs[k].has_arg != 0;
-      if (is_distinct(a.func)) {
-        // the reference's partial state of a DISTINCT aggregate is a List column, which has no device form: single-stage modes only
+      if (cells_at_emit(a.func)) {
+        // the reference's partial state of a DISTINCT aggregate and of MEDIAN is a List column, which has no device form: single-stage modes only
         static const char* const MODE_NAMES[] = {"Partial", "Final", "FinalPartitioned", "Single", "SinglePartitioned", "PartialReduce"};
-        const std::string who = std::string(distinct_name(a.func)) + " (aggregate " + (aggs[k].name ? aggs[k].name : "") + ")";
+        const std::string who = std::string(is_holistic(a.func) ? "MEDIAN" : distinct_name(a.func)) + " (aggregate " + (aggs[k].name ? aggs[k].name : "") + ")";
         DFGPU_CHECK(mode == DFGPU_AGG_SINGLE || mode == DFGPU_AGG_SINGLE_PARTITIONED,
                     who + " is not supported in mode " + MODE_NAMES[mode] + " on the GPU path: its partial state is a List column");
         DFGPU_CHECK(a.has_arg && aggs[k].arg.nodes && aggs[k].arg.n_nodes >= 1, who + " needs an argument");
@@ -5496,20 +5824,23 @@ int dfgpu_agg_create(int mode, const dfgpu_expr* group_by, const char* const* gr
           a.filter_pool.assign(f.string_pool, pool);
         }
       }
-      if (is_distinct(a.func)) {
-        // two aggregates over the same argument expression and filter share one set
+      if (cells_at_emit(a.func)) {
+        // two aggregates over the same argument expression and filter share one set (DISTINCT) or one row store (MEDIAN)
         auto same_nodes = [](const std::vector<dfgpu_expr_node>& x, const std::vector<dfgpu_expr_node>& y) {
           return x.size() == y.size() && (x.empty() || std::memcmp(x.data(), y.data(), x.size() * sizeof(dfgpu_expr_node)) == 0);
         };
         bool literal_strings = false;   // (an argument's string literals live in a pool that is not compared here)
         for (const dfgpu_expr_node& nd : a.nodes) literal_strings |= nd.op == DFGPU_EXPR_LITERAL && nd.field.type == DFGPU_UTF8;
         for (const AggState& b : A->aggs)
-          if (!literal_strings && is_distinct(b.func) && b.root == a.root && same_nodes(b.nodes, a.nodes) && b.has_filter == a.has_filter &&
-              b.filter_root == a.filter_root && same_nodes(b.filter_nodes, a.filter_nodes) && b.filter_pool == a.filter_pool) {
+          if (!literal_strings && is_distinct(b.func) == is_distinct(a.func) && is_holistic(b.func) == is_holistic(a.func) && b.root == a.root &&
+              same_nodes(b.nodes, a.nodes) && b.has_filter == a.has_filter && b.filter_root == a.filter_root && same_nodes(b.filter_nodes, a.filter_nodes) &&
+              b.filter_pool == a.filter_pool) {
             a.dset = b.dset;
+            a.mstore = b.mstore;
             break;
           }
-        if (!a.dset) a.dset = std::make_shared<DistinctSet>();
+        if (is_distinct(a.func) && !a.dset) a.dset = std::make_shared<DistinctSet>();
+        if (is_holistic(a.func) && !a.mstore) a.mstore = std::make_shared<MedianStore>();
       }
       A->aggs.push_back(std::move(a));
     }
@@ -5530,8 +5861,8 @@ int dfgpu_agg_create_grouping_sets(int mode, const dfgpu_expr* group_by, const d
                 "grouping sets: Final modes group by the partial state's key columns (the n_group keys and __grouping_id): use dfgpu_agg_create");
     DFGPU_CHECK(group_by && null_by && groups && n_group >= 1 && n_group <= 63 && n_sets >= 1 && out, "grouping sets: bad argument");
     for (int k = 0; k < n_aggs; k++)
-      DFGPU_CHECK(!is_distinct(aggs[k].func), std::string("grouping sets: ") + distinct_name(aggs[k].func) + " (aggregate " + (aggs[k].name ? aggs[k].name : "") +
-                                                  ") is not supported on the GPU path");
+      DFGPU_CHECK(!cells_at_emit(aggs[k].func), std::string("grouping sets: ") + (is_holistic(aggs[k].func) ? "MEDIAN" : distinct_name(aggs[k].func)) + " (aggregate " +
+                                                    (aggs[k].name ? aggs[k].name : "") + ") is not supported on the GPU path");
     auto top = std::make_unique<Aggregate>();
     top->mode = mode;
     // Aggregate::grouping_id_type: UInt8 / UInt16 / UInt32 / UInt64 by the number of grouping columns.  The device has no UInt16

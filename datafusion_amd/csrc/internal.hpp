@@ -466,7 +466,9 @@ Column mark_column(const uint8_t* bytes, int64_t n);
 
 // ----------------------------------------------------------------- radix passes (sort.hip)
 // (key u64, row id u32) pairs stably sorted by bits [lo_bit, lo_bit + nbits) of the key; `idx` null on entry = row id is the position
-void radix_sort_pairs(BufPtr& key, BufPtr& idx, int64_t n, int lo_bit, int nbits);
+// keep_input: the buffers handed in are only read (the passes otherwise write into them from the second pass on); key / idx leave as fresh buffers,
+// or as they came when there is nothing to sort
+void radix_sort_pairs(BufPtr& key, BufPtr& idx, int64_t n, int lo_bit, int nbits, bool keep_input = false);
 // keys alone, grouped stably by bits [lo_bit, lo_bit + nbits) of their value (no row ids are made)
 void radix_group_keys(BufPtr& key, int64_t n, int lo_bit, int nbits);
 Table sort_table_ascending(const Table& in, const std::vector<int>& key_cols);   // sort.hip; stable

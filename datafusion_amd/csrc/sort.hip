@@ -886,7 +886,7 @@ static BufPtr iota_ids(int64_t n) {
 }
 
 // stable LSD radix sort of n (key, idx) elements over the given digits; returns the buffers holding the result
-static SortedKeys radix_sort(SortedKeys in, int64_t n, const std::vector<Digit>& digits, bool want_ids = true) {
+static SortedKeys radix_sort(SortedKeys in, int64_t n, const std::vector<Digit>& digits, bool want_ids = true, bool keep_input = false) {
   Runtime& r = rt();
   if (n <= 1 || digits.empty()) return in;
   const int nwords = in.nwords;
@@ -922,6 +922,10 @@ static SortedKeys radix_sort(SortedKeys in, int64_t n, const std::vector<Digit>&
     }
     DFGPU_HIP(hipGetLastError());
     std::swap(cur, alt);
+    if (keep_input && &d == &digits.front()) {   // `alt` now names the caller's buffers: the later passes get buffers of their own
+      for (int wd = 0; wd < nwords; wd++) alt.w[wd] = make_buf((size_t)n * 8);
+      alt.idx = want_ids ? make_buf((size_t)n * 4) : nullptr;
+    }
   }
   return cur;
 }
@@ -1718,12 +1722,12 @@ static BufPtr sorted_ids_local(const SortedKeys& sk, int64_t n, const KeyPlan& k
 // (key, row id) pairs sorted by bits [lo_bit, lo_bit + nbits) of the key — the radix partitioning of the LDS hash join
 // (radix_join.hip): nbits / 8 stable passes.  `idx` may be null on entry: the row id of pair i is then i.
 // 6-bit digits: a 64-way scatter of a 4096-row tile writes 64-row runs; 256-way passes cost 2x per pass (profiles/r2_radix_sweep.md)
-void radix_sort_pairs(BufPtr& key, BufPtr& idx, int64_t n, int lo_bit, int nbits) {
+void radix_sort_pairs(BufPtr& key, BufPtr& idx, int64_t n, int lo_bit, int nbits, bool keep_input) {
   if (n <= 1 || nbits <= 0) {
     if (!idx) idx = iota_ids(n);
     return;
   }
-  SortedKeys out = radix_sort(one_word_keys(key, idx), n, equal_digits(0, lo_bit, nbits, 6));
+  SortedKeys out = radix_sort(one_word_keys(key, idx), n, equal_digits(0, lo_bit, nbits, 6), /*want_ids=*/true, keep_input);
   key = out.w[0];
   idx = out.idx;
 }

@@ -22,12 +22,19 @@ AGG_FUNCS = {"sum": 0, "min": 1, "max": 2, "count": 3, "avg": 4, "var": 5, "var_
              # bit_and_or_xor.rs, bool_and_or.rs: one fixed-width state per group, exact
              "bit_and": 9, "bit_or": 10, "bit_xor": 11, "bool_and": 12, "bool_or": 13,
              # ABI 21: COUNT(DISTINCT x) / SUM(DISTINCT x), a device-resident set of (group, value) per argument; Single modes only
-             "count_distinct": 14, "sum_distinct": 15}
+             "count_distinct": 14, "sum_distinct": 15,
+             # ABI 22: MEDIAN(x), dfgpu_agg_func_ordered: a device-resident row store per argument, sorted when the node emits; Single modes only
+             "median": 16}
 VARIANCE_FUNCS = frozenset(f for f, i in AGG_FUNCS.items() if 5 <= i <= 8)
 BITWISE_FUNCS = frozenset(("bit_and", "bit_or", "bit_xor"))
 BOOLEAN_FUNCS = frozenset(("bool_and", "bool_or"))
 DISTINCT_FUNCS = frozenset(("count_distinct", "sum_distinct"))
 DISTINCT_NAMES = {"count_distinct": "COUNT(DISTINCT)", "sum_distinct": "SUM(DISTINCT)"}     # as the library's refusals spell them
+HOLISTIC_FUNCS = frozenset(("median",))
+HOLISTIC_NAMES = {"median": "MEDIAN"}
+# the aggregates whose partial state is a List column in the reference: no device partial state, single-stage modes only
+NO_PARTIAL_STATE_FUNCS = DISTINCT_FUNCS | HOLISTIC_FUNCS
+NO_PARTIAL_STATE_NAMES = {**DISTINCT_NAMES, **HOLISTIC_NAMES}
 GPU_MIN_KEY_DENSITY = 1.0 / 64.0      # DFGPU_DEFAULT_MIN_KEY_DENSITY (include/dfgpu.h); the reference's CPU default is 0.15
 TABLE_MODES = {"auto": 0, "hash_map": 1, "array_map": 2, "rank_map": 3}
 # dfgpu_window_func / dfgpu_window_frame (include/dfgpu.h); WINDOW_TILE = DFGPU_WINDOW_TILE, the rows one workgroup of the window's

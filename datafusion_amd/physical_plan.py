@@ -618,7 +618,8 @@ _EXCHANGE_NODES = (RepartitionExec, CoalesceBatchesExec, CoalescePartitionsExec,
 
 
 def _has_distinct(node) -> bool:
-    return any(f in ops.DISTINCT_FUNCS for f, _, _, _ in ops.normalize_aggs(node.aggr_expr))
+    """has an aggregate without a device partial state: a DISTINCT aggregate or a MEDIAN (the reference's state is a List column)"""
+    return any(f in ops.NO_PARTIAL_STATE_FUNCS for f, _, _, _ in ops.normalize_aggs(node.aggr_expr))
 
 
 def _aggr_detail(aggr_expr):
@@ -849,7 +850,7 @@ class GpuOffloadRule:
         return plan
 
     def _decline_orphan_partials(self, node: ExecutionPlan):
-        """a Partial node with a DISTINCT aggregate that no Final parent collapsed (see _rewrite) stays the reference's operator"""
+        """a Partial node with a DISTINCT aggregate or a MEDIAN that no Final parent collapsed (see _rewrite) stays the reference's operator"""
         if isinstance(node, AggregateExec) and node.mode == "Partial" and _has_distinct(node) and not getattr(node, "kept_on_cpu", False):
             node.kept_on_cpu = True
             self.declined.append((node, unsupported_reason(node)))
@@ -888,7 +889,7 @@ class GpuOffloadRule:
             self.declined.append((node, f"{node.name()} on {self.world_size} ranks: the nested loop join is only exercised on one rank"))
             return node
         if isinstance(node, AggregateExec) and self.world_size == 1 and _has_distinct(node) and not getattr(node, "kept_on_cpu", False):
-            # DISTINCT aggregates have no device partial state.  On one rank the exchange between Final and Partial is gone already and
+            # DISTINCT aggregates and MEDIAN have no device partial state.  On one rank the exchange between Final and Partial is gone already and
             # Final o Partial == Single: the Partial is left as it is when it is visited, and the pair becomes ONE Single node — the
             # Partial's expressions over the Partial's input, the Final's output names — when its Final parent is
             if node.mode == "Partial":
@@ -1128,7 +1129,7 @@ def _agg_type(func, t):
         return pa.decimal128(min(38, t.precision + 4), min(38, t.scale + 4)) if pa.types.is_decimal128(t) else pa.float64()   # average.rs:219-252
     if func in ops.VARIANCE_FUNCS:
         return pa.float64()     # variance.rs / stddev.rs return_type
-    return t    # min / max; bit_and / bit_or / bit_xor and bool_and / bool_or: the argument's type (bit_and_or_xor.rs, bool_and_or.rs)
+    return t    # min / max; bit_and / bit_or / bit_xor and bool_and / bool_or; median: the argument's type (bit_and_or_xor.rs, bool_and_or.rs, median.rs)
 
 
 def _device_type_name(t):
@@ -1140,6 +1141,23 @@ def _device_type_name(t):
     names = {pa.int32(): "Int32", pa.int64(): "Int64", pa.float64(): "Float64", pa.uint8(): "UInt8", pa.uint32(): "UInt32", pa.uint64(): "UInt64",
              pa.date32(): "Date32", pa.bool_(): "Boolean"}
     return names.get(t, str(t))
+
+
+def _argument_type(node, inp, e, t):
+    """the type an aggregate's type check sees for argument `e` typed as `t`: the device types a dictionary-encoded string column by its
+    codes (Int32), while the library's checks know the column has a dictionary (aggregate.hip distinct_check_type, median_check_type:
+    `v.dict`).  The input's schema says so for an Arrow source, the device table itself for a scan of one; anything else is `t`."""
+    import pyarrow as pa
+    if not isinstance(e, Column):
+        return t
+    src = inp.field(inp.get_field_index(e.name) if e.index is None else e.index).type
+    if pa.types.is_dictionary(src):
+        return src
+    scan = node.input
+    if isinstance(scan, MemoryExec) and scan.projection is None and hasattr(scan.table, "dictionary_size") \
+            and scan.table.dictionary_size(e.name if e.index is None else e.index) is not None:
+        return pa.dictionary(pa.int32(), pa.string())
+    return t
 
 
 def _key_bits(t):
@@ -1159,13 +1177,13 @@ def unsupported_reason(node):
     operator instead of failing the query — every entry here has a test that feeds a plan through GpuOffloadRule."""
     import pyarrow as pa
     if isinstance(node, (AggregateExec, GpuFusedAggregateExec)):
-        # aggregate.hip dfgpu_agg_create: a DISTINCT aggregate's partial state is a List column in the reference, so the device takes
+        # aggregate.hip dfgpu_agg_create: a DISTINCT aggregate's and a MEDIAN's partial state is a List column in the reference, so the device takes
         # the single-stage modes only (known without typing anything: a plan without a device is told the same)
         for func, e, n, _ in ops.normalize_aggs(node.aggr_expr):
-            if func in ops.DISTINCT_FUNCS and e is None:
-                return f"{ops.DISTINCT_NAMES[func]} (aggregate {n}) needs an argument"
-            if func in ops.DISTINCT_FUNCS and node.mode not in ("Single", "SinglePartitioned"):
-                return f"{ops.DISTINCT_NAMES[func]} (aggregate {n}) is not supported in mode {node.mode} on the GPU path: its partial state is a List column"
+            if func in ops.NO_PARTIAL_STATE_FUNCS and e is None:
+                return f"{ops.NO_PARTIAL_STATE_NAMES[func]} (aggregate {n}) needs an argument"
+            if func in ops.NO_PARTIAL_STATE_FUNCS and node.mode not in ("Single", "SinglePartitioned"):
+                return f"{ops.NO_PARTIAL_STATE_NAMES[func]} (aggregate {n}) is not supported in mode {node.mode} on the GPU path: its partial state is a List column"
     if isinstance(node, (AggregateExec, GpuFusedAggregateExec)) and node.mode in ("Single", "SinglePartitioned", "Partial"):
         inp = plan_schema(node.input)
         if inp is None:
@@ -1194,6 +1212,17 @@ def unsupported_reason(node):
                     return f"{func}({e!r}): {err}"
                 except (KeyError, TypeError, ValueError):
                     continue   # not typable from this schema (a name the input does not carry): decided at run time
+                if func in ops.NO_PARTIAL_STATE_FUNCS:
+                    t = _argument_type(node, inp, e, t)
+                if func in ops.HOLISTIC_FUNCS:
+                    # aggregate.hip median_check_type, in its words
+                    if pa.types.is_boolean(t):
+                        return "MEDIAN over Boolean is not supported on the GPU path"
+                    if pa.types.is_string(t) or pa.types.is_large_string(t) or pa.types.is_dictionary(t):
+                        return "MEDIAN over Utf8 is not supported on the GPU path"
+                    if not (pa.types.is_decimal128(t) or t in (pa.int32(), pa.int64(), pa.uint8(), pa.uint32(), pa.uint64(), pa.float64())):
+                        return f"MEDIAN over {_device_type_name(t)} is not supported on the GPU path"
+                    continue
                 if func in ops.DISTINCT_FUNCS:
                     # aggregate.hip distinct_check_type, in its words (type_name's spelling for every type the device has)
                     what, stringy = ops.DISTINCT_NAMES[func], pa.types.is_string(t) or pa.types.is_large_string(t) or pa.types.is_dictionary(t)

@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define DFGPU_ABI_VERSION 21
+#define DFGPU_ABI_VERSION 22
 
 /* Arrow C Data Interface (https://arrow.apache.org/docs/format/CDataInterface.html) */
 #ifndef ARROW_C_DATA_INTERFACE
@@ -646,6 +646,36 @@ typedef enum dfgpu_agg_func {
   DFGPU_AGG_BIT_AND = 9, DFGPU_AGG_BIT_OR = 10, DFGPU_AGG_BIT_XOR = 11, DFGPU_AGG_BOOL_AND = 12, DFGPU_AGG_BOOL_OR = 13,
   DFGPU_AGG_COUNT_DISTINCT = 14, DFGPU_AGG_SUM_DISTINCT = 15
 } dfgpu_agg_func;
+/* The ordered (holistic) aggregates (ABI 22).  The values continue dfgpu_agg_func's and go into the same field, dfgpu_agg_spec.func.
+ * MEDIAN(x) (functions-aggregate/src/median.rs, calculate_median) over a group: NULL arguments are skipped, and with a FILTER the rows
+ * whose filter is not TRUE; let v[0..c) be the remaining values in ascending order.
+ *   c == 0: NULL.   c odd: v[c / 2], its bits unchanged.
+ *   c even: lo = v[c / 2 - 1], hi = v[c / 2], the result is (lo + hi) / 2 in the argument's own native type: the addition is
+ *     add_wrapping, the division div_wrapping.
+ *   Int32 / Int64 / UInt8 / UInt32 / UInt64: the sum wraps at the type's width and is then divided by 2, truncating toward zero —
+ *     Int32 {2147483647, 2147483647} gives -1, UInt8 {200, 200} gives 72, Int64 {-3, 0} gives -1 (a truncation, not a floor).
+ *   Decimal128(p, s): the unscaled 128-bit integers, the sum wrapping at 128 bits, / 2 truncating toward zero; the result is
+ *     Decimal128(p, s).
+ *   Float64: the order is IEEE totalOrder (-NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN).  Odd count: the bits are unchanged
+ *     (NaN payloads and -0.0 survive).  Even count: one IEEE addition, then one IEEE division by 2.0, each rounded once — no fused
+ *     operation, no fast-math; {1e308, 1e308} gives +inf.
+ *   The result type is the argument's type, nullable.
+ *   Argument types: Int32, Int64, UInt8, UInt32, UInt64, Float64, Decimal128.  Anything else is refused at the first update that
+ *     shows the type ("MEDIAN over Date32 is not supported on the GPU path", "... over Boolean ...", and "... over Utf8 ..." for Utf8
+ *     and dictionary-encoded strings).
+ *   Modes: Single and SinglePartitioned.  The reference's partial state is a List column: any other mode is refused by
+ *     dfgpu_agg_create ("MEDIAN (aggregate <name>) is not supported in mode <Mode> on the GPU path: its partial state is a List
+ *     column"), a spec without an argument too ("MEDIAN (aggregate <name>) needs an argument"), and any mode by
+ *     dfgpu_agg_create_grouping_sets, by name.
+ *   Memory: the node stores every non-NULL argument row for its whole life — 12 bytes per row (a 32-bit group number and a 64-bit
+ *     orderable key), 20 for Decimal128 — in a store that grows by doubling, every growth admitted by the pool; aggregates over the
+ *     same argument and filter share one store.  While the node emits, the sort's temporaries exist as well: 64-bit keys and 32-bit
+ *     row ids, double-buffered (24 bytes per stored row).  More than 2^31 - 2 stored values in one aggregate are refused by name: the
+ *     sort's row ids are 32 bits.
+ *   Option agg.median_rows (test hook: 0 = the first batch's rows): the elements a store starts with; 64 makes small inputs grow it.
+ *   Not taken: MEDIAN(DISTINCT), approx_median / approx_percentile_cont, Float32 and the narrow integer types the device does not
+ *     have, the staged modes and several ranks, grouping sets. */
+typedef enum dfgpu_agg_func_ordered { DFGPU_AGG_MEDIAN = 16 } dfgpu_agg_func_ordered;
 typedef struct dfgpu_agg_spec {
   int32_t func;          /* dfgpu_agg_func */
   int32_t has_arg;       /* 0 = COUNT(*) */
@@ -700,6 +730,7 @@ int dfgpu_agg_fused_updates(dfgpu_agg_t h, int64_t* out);
  *   jit.cache = 0|1 (1), jit.cache_dir  on-disk cache of compiled nodes; jit.dump_dir: generated sources are written there
  *   agg.partitioned = 0|1 (1), agg.partitioned_min_rows (2 x rows worth a pass), agg.grouped_move, agg.direct_table, agg.runs = 0|1 (1)
  *   agg.distinct_slots (test hook: 0 = derived; the slots a DISTINCT aggregate's set starts with: 64 makes small inputs grow it)
+ *   agg.median_rows (test hook: 0 = derived; the elements a MEDIAN's row store starts with: 64 makes small inputs grow it)
  *   join.grouped_probe = 0|1 (1), join.grouped_min_rows (rows worth a pass), join.beyond_cache_bytes (4 x the L2 of an XCD),
  *   join.grouped_bits, join.near_window (test hooks: 0 = derived)
  *   join.share_probe = 0|1 (1: an all-hit probe in probe order hands back the probe table's own columns, dfgpu_join_probe),
